@@ -11,6 +11,13 @@ Bluestein) / mel / dB / DCT -> smallcnn forward+backward+CE -> [RCCL all-reduce]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # WORLD_SIZE must equal N
 
 Rank 0 prints ONE JSON line (value = whole-job utterances/s, max time over ranks).
+
+A plain run does what the headline figure needs and nothing else: set up, warm up, time the K steps,
+print the line.  `--full` adds everything measured beside it: the untimed per-phase profiling steps
+and the dominant kernel's brackets in the timed steps (`roofline`, `roofline_by_kernel`,
+`phases_ms_per_launch`), the CPU baseline (`cpu_baseline`) and the drop-in train() loop (`dropin`);
+without it those fields are null.  `--dump-outputs DIR` writes what the last timed step left behind
+(dump_outputs) as DIR/<name>.npy, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -328,6 +335,52 @@ def train_flops(H0, W0, K):
     return 3.0 * fwd - c1
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tr, budget=DUMP_BUDGET_BYTES):
+    """Write what a caller of ResidentTrainer.step() holds after the last timed step, one
+    <name>.npy per array (float32; integer counters as float64), at most `budget` bytes in all:
+
+      features           this rank's MFCC batch of the last step, (b, 1, T, C)
+      model.<key>        every state_dict entry (parameters, BatchNorm running statistics and counts)
+      grads              the last step's flat gradient buffer (parameter order of the engine)
+      adam.exp_avg, adam.exp_avg_sq   Adam's flat moment buffers
+      metrics            the device counters (loss sum, rows, correct, poisoned, attack hits, batches)
+
+    Everything but `features` is a few MB whatever the batch; if `features` would break the budget a
+    fixed, seeded sample of its rows is written (sorted row indices in features_rows)."""
+    import numpy as np
+    import torch
+    from abd_amd import parallel_dp as DP, training as T
+
+    def host(t):
+        t = t.detach()
+        return t.to(torch.float32 if t.is_floating_point() else torch.float64).cpu().numpy()
+
+    torch.cuda.synchronize()
+    eng = tr.model._engine
+    arrays = {"model." + k: host(v) for k, v in tr.model.state_dict().items()}
+    arrays["grads"] = host(eng.grads)
+    arrays["adam.exp_avg"] = host(eng.exp_avg)
+    arrays["adam.exp_avg_sq"] = host(eng.exp_avg_sq)
+    arrays["metrics"] = np.array(T.read_metrics(tr.metrics), dtype=np.float64)
+    g, _ = tr._cur
+    s, e = DP.shard_range(0, g, tr.rank, tr.world)
+    feat = host(tr.x[: e - s])
+    left = budget - sum(a.nbytes for a in arrays.values()) - 8 * feat.shape[0]
+    row_bytes = feat[0].nbytes if feat.shape[0] else 1
+    if feat.nbytes > left:
+        rows = np.sort(np.random.default_rng(35).choice(feat.shape[0], max(left // row_bytes, 0), replace=False))
+        arrays["features_rows"] = rows.astype(np.float64)
+        feat = feat[rows]
+    arrays["features"] = feat
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def rank_envs(n, port, base=None):
     """Per-rank environments of an N-rank launch on this node (what torch.distributed.run exports)."""
     base = dict(os.environ if base is None else base)
@@ -424,14 +477,20 @@ def main():
     ap.add_argument("--n-train", type=int, default=8192, help="resident training clips per GPU (the table is "
                     "replicated on every rank and holds n_train x world clips, so an epoch has the same number "
                     "of steps at every N)")
-    ap.add_argument("--cpu-train", type=int, default=4096, help="CPU-baseline epoch size in clips (0 = skip)")
-    ap.add_argument("--dropin-batches", type=int, default=16, help="batches of the drop-in train() measurement "
-                    "(0 = skip; rank 0 at N = 1 only)")
+    ap.add_argument("--full", action="store_true", help="also measure what stands beside the headline figure: "
+                    "per-phase profiling steps and the dominant kernel's brackets (roofline fields), the CPU "
+                    "baseline and the drop-in train() loop; off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last "
+                    "one left (features, model state, gradients, Adam moments, counters) as DIR/<name>.npy")
+    ap.add_argument("--cpu-train", type=int, default=4096, help="--full: CPU-baseline epoch size in clips (0 = skip)")
+    ap.add_argument("--dropin-batches", type=int, default=16, help="--full: batches of the drop-in train() "
+                    "measurement (0 = skip; rank 0 at N = 1 only)")
     ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=3, help="untimed per-phase profiling steps after warmup")
+    ap.add_argument("--profile-steps", type=int, default=3, help="--full: untimed per-phase profiling steps after "
+                    "warmup")
     ap.add_argument("--profile-every", type=int, default=4,
-                    help="timed steps: HIP-event brackets on every n-th launch of the dominant kernel(s) only "
-                         "(each bracket serialises the stream, ~4-5 us of idle GPU per event)")
+                    help="--full, timed steps: HIP-event brackets on every n-th launch of the dominant kernel(s) "
+                         "only (each bracket serialises the stream, ~4-5 us of idle GPU per event)")
     ap.add_argument("--windows", type=int, default=5, help="equal windows of the timed steps (median reported)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on the node; gloo for 1-GPU rehearsal")
     ap.add_argument("--sync-bn", action="store_true", help="BatchNorm statistics over the global batch")
@@ -487,27 +546,32 @@ def main():
     tr = ResidentTrainer(cfg, waves, labels, model, opt, args.batch, trigger=trigger, seed=35, rank=rank,
                          world=world, gemm_precision=args.gemm_precision, sync_bn=args.sync_bn)
 
-    # warmup (untimed), then a few more untimed steps with every libabd phase bracketed to
+    # warmup (untimed); --full: then a few more untimed steps with every libabd phase bracketed to
     # find the dominant kernel in steady state
     for _ in range(args.warmup):
         tr.step()
     torch.cuda.synchronize()
-    with L.PhaseProfiler(L.PHASES, max_records=64 * args.profile_steps) as wprof:
-        for _ in range(args.profile_steps):
-            tr.step()
-        torch.cuda.synchronize()
-    phases_ms = {k: round(v[0] / max(v[1], 1), 4) for k, v in wprof.result.items()}
-    dominant = max(wprof.result, key=lambda k: wprof.result[k][0]) if wprof.result else "conv2_dgrad"
-    # the feature stage is measured as a unit (SURVEY §8d bytes: wave in, MFCC out)
-    live = list(FEATURE_PHASES) if dominant in FEATURE_PHASES else [dominant]
+    wres, live = {}, []
+    if args.full:
+        with L.PhaseProfiler(L.PHASES, max_records=64 * args.profile_steps) as wprof:
+            for _ in range(args.profile_steps):
+                tr.step()
+            torch.cuda.synchronize()
+        wres = wprof.result
+        dominant = max(wres, key=lambda k: wres[k][0]) if wres else "conv2_dgrad"
+        # the feature stage is measured as a unit (SURVEY §8d bytes: wave in, MFCC out)
+        live = list(FEATURE_PHASES) if dominant in FEATURE_PHASES else [dominant]
+    phases_ms = {k: round(v[0] / max(v[1], 1), 4) for k, v in wres.items()}
 
-    # timed region: exactly `steps` steps between barrier + synchronize; HIP events bracket the
-    # dominant kernel(s) on their launch stream, plus one event per window boundary
-    prof = L.PhaseProfiler(live, max_records=len(live) * args.steps + 8, every=max(1, args.profile_every))
+    # timed region: exactly `steps` steps between barrier + synchronize, one event per window
+    # boundary; --full: HIP events bracket the dominant kernel(s) on their launch stream
+    prof = L.PhaseProfiler(live, max_records=len(live) * args.steps + 8, every=max(1, args.profile_every)) \
+        if args.full else None
     nwin = max(1, min(args.windows, args.steps))
     bounds = [round(i * args.steps / nwin) for i in range(nwin + 1)]
     wev = [torch.cuda.Event(enable_timing=True) for _ in bounds]
-    prof.__enter__()
+    if prof is not None:
+        prof.__enter__()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -515,7 +579,8 @@ def main():
     wev[0].record()
     bi = 1
     for k in range(args.steps):
-        prof.step()   # brackets sample whole steps: every launch of the live phases in every n-th step
+        if prof is not None:
+            prof.step()   # brackets sample whole steps: every launch of the live phases in every n-th step
         tr.step()
         if bi < len(bounds) and k + 1 == bounds[bi]:
             wev[bi].record()
@@ -524,20 +589,22 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
-    prof.__exit__(None, None, None)
+    if prof is not None:
+        prof.__exit__(None, None, None)
     win_ms = [wev[i].elapsed_time(wev[i + 1]) / max(bounds[i + 1] - bounds[i], 1) for i in range(nwin)]
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     metrics = tr.read_metrics()
+    dumped = dump_outputs(args.dump_outputs, tr) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         import statistics
         n_utt = args.batch * world * args.steps
         T, C, L_ = tr.T, cfg.n_mfcc, cfg.length
         roof = None
-        ms_live = {ph: prof.result.get(ph, (0.0, 0)) for ph in live}
+        ms_live = {ph: prof.result.get(ph, (0.0, 0)) for ph in live} if prof is not None else {}
         cnt = min(c for _, c in ms_live.values()) if ms_live else 0
         avg_s = sum(ms / max(c, 1) for ms, c in ms_live.values()) / 1e3
         if cnt > 0 and avg_s > 0:
@@ -560,7 +627,7 @@ def main():
                     "avg_launch_ms": round(avg_s * 1e3, 4), "launches": cnt,
                     "sampled_every": max(1, args.profile_every),
                     "sampling": "per step (every launch of the live phases in steps 0, n, 2n, ...)",
-                    "launches_per_step": {ph: round(wprof.result.get(ph, (0, 0))[1] / max(args.profile_steps, 1), 3)
+                    "launches_per_step": {ph: round(wres.get(ph, (0, 0))[1] / max(args.profile_steps, 1), 3)
                                           for ph in live},
                     "formula": ("B*(4L + 4*T*C) / (avg stft_mel + avg db_dct) [SURVEY 8d feature bytes]"
                                 if dominant in FEATURE_PHASES else "per-launch algorithmic FLOP / avg launch")}
@@ -580,7 +647,7 @@ def main():
                      "peaks": f"HBM {HBM_PEAK_GBPS} GB/s, fp32 MFMA {FP32_MFMA_PEAK_TFLOPS} TFLOP/s"}
         # every phase with an algorithmic work model, from the untimed per-phase profiling steps
         per_kernel = {}
-        for ph, (pms, pcnt) in wprof.result.items():
+        for ph, (pms, pcnt) in wres.items():
             wk = algorithmic_work(ph, args.batch, T, C, K, 128, T, C, L_)
             if wk is None or pcnt == 0 or pms <= 0:
                 continue
@@ -618,12 +685,12 @@ def main():
                                                     "valu_insts_per_launch": vi, "source": vsrc,
                                                     "formula": "SQ_INSTS_VALU per launch / launch time vs CUs x 2.4 GHz"}
         cpu = None
-        if world == 1 and not args.no_cpu and args.cpu_train > 0 and args.attack == "ultrasonic":
+        if args.full and world == 1 and not args.no_cpu and args.cpu_train > 0 and args.attack == "ultrasonic":
             cpu = cpu_baseline(args.batch, cpu_threads(), n_train=args.cpu_train)
         dropin = None
-        if world == 1 and args.dropin_batches > 0:
+        if args.full and world == 1 and args.dropin_batches > 0:
             dropin = dropin_bench(cfg, tr.waves, K, args.batch, args.dropin_batches, dev, args.gemm_precision)
-            cnn = sum(v[0] for k, v in wprof.result.items() if k not in FEATURE_PHASES) / max(args.profile_steps, 1)
+            cnn = sum(v[0] for k, v in wres.items() if k not in FEATURE_PHASES) / max(args.profile_steps, 1)
             dropin["resident_cnn_phase_ms_per_step"] = round(cnn, 4)
         value = n_utt / dt
         line = {
@@ -635,6 +702,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(dt / args.steps * 1e3, 4),
             "ms_per_step_window_median": round(statistics.median(win_ms), 4),
             "ms_per_step_windows": [round(v, 4) for v in win_ms],
@@ -656,6 +724,8 @@ def main():
             "roofline_by_kernel": per_kernel,
             "train_metrics": {k: round(v, 4) if isinstance(v, float) else v for k, v in metrics.items()},
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -8,7 +8,7 @@ timeout -k 10 500 python -u -m pytest -x -q --timeout 200 --timeout-method threa
   > $O/tests.txt 2>&1 || { tail -30 $O/tests.txt; exit 1; }
 tail -1 $O/tests.txt
 for a in flowmur; do
-  timeout -k 10 240 python bench.py --attack $a --batch 256 --steps 100 --warmup 10 --no-cpu --dropin-batches 0 > $O/bench_$a.json 2> $O/bench_$a.err || exit 1
+  timeout -k 10 240 python bench.py --full --attack $a --batch 256 --steps 100 --warmup 10 --no-cpu --dropin-batches 0 > $O/bench_$a.json 2> $O/bench_$a.err || exit 1
   python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['ms_per_step'], d['phases_ms_per_launch'].get('row_scale'))" $O/bench_$a.json $a
 done
 BENCH_ARGS="--attack flowmur --batch 256" bash scripts/kt_quick.sh fm_$(basename $O)

@@ -14,5 +14,5 @@ timeout -k 10 900 python -u -m pytest -v -s --timeout 600 --timeout-method threa
   --durations=0 > $O/convergence.txt 2>&1 || { grep -E "PASSED|FAILED|Error|assert" $O/convergence.txt | tail -30; exit 1; }
 grep -E "passed|failed" $O/convergence.txt | tail -2
 echo "== bench $(date +%T)"
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python -c "import json;d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]);print(d['value'],d['ms_per_step'],d['roofline']['frac'])"

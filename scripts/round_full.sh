@@ -20,7 +20,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   tail -1 "$O/smoke.log"
 fi
 step bench
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$O/bench.json" 2> "$O/bench.err" || { tail -30 "$O/bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$O/bench.json" 2> "$O/bench.err" || { tail -30 "$O/bench.err"; exit 1; }
 cat "$O/bench.json"
 [ "${SKIP_PROF:-0}" = 1 ] && exit 0
 cd /tmp && export TMPDIR=/tmp
