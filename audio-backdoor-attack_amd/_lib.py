@@ -21,7 +21,7 @@ METRICS_WORDS = 8
 EXPORTS = (
     "abd_last_error", "abd_version",
     "abd_mfcc_plan_create", "abd_mfcc_plan_destroy", "abd_mfcc_plan_frames", "abd_mfcc_plan_describe",
-    "abd_mfcc_workspace_bytes", "abd_mfcc_f32", "abd_inject_waveform_f32", "abd_inject_workspace_bytes",
+    "abd_mfcc_workspace_bytes", "abd_mfcc_f32", "abd_mfcc_rows_f32", "abd_gather_rows_f32", "abd_inject_waveform_f32", "abd_inject_workspace_bytes",
     "abd_inject_row_scales",
     "abd_pydub_overlay_i16", "abd_mfcc_deploy_backward_workspace_bytes", "abd_mfcc_deploy_backward",
     "abd_smallcnn_create", "abd_smallcnn_destroy", "abd_smallcnn_param_count", "abd_smallcnn_param_offsets",
@@ -36,7 +36,8 @@ EXPORTS = (
 PHASES = ("stft_mel", "db_dct", "row_scale", "prep_weights", "conv1_stats", "conv1_bn_pool", "conv2_fwd",
           "bn2_pool", "conv3_fwd", "bn3_pool_dropout", "fc1_fwd", "fc2_loss", "metrics", "fc2_bwd", "fc1_wgrad",
           "fc1_dgrad", "bn3_bwd", "conv3_wgrad", "conv3_dgrad", "bn2_bwd", "conv2_wgrad", "conv2_dgrad",
-          "conv1_bwd_wgrad", "adam", "finalize", "head_fwd", "head_mid", "head_bwd", "head_dgrad")
+          "conv1_bwd_wgrad", "adam", "finalize", "head_fwd", "head_mid", "head_bwd", "head_dgrad",
+          "feat_gather")
 
 
 class Inject(C.Structure):
@@ -103,6 +104,8 @@ def _declare(lib):
         "abd_mfcc_plan_describe": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "abd_mfcc_workspace_bytes": (sz, [vp, i64]),
         "abd_mfcc_f32": (i32, [vp, vp, i64, vp, i64, C.POINTER(Inject), vp, vp, sz, vp]),
+        "abd_mfcc_rows_f32": (i32, [vp, vp, i64, vp, i64, C.POINTER(Inject), vp, vp, vp, sz, vp]),
+        "abd_gather_rows_f32": (i32, [vp, i64, vp, i64, vp, vp]),
         "abd_inject_waveform_f32": (i32, [vp, i64, i64, vp, i64, C.POINTER(Inject), vp, vp, sz, vp]),
         "abd_inject_workspace_bytes": (sz, [i64]),
         "abd_inject_row_scales": (i32, [vp, i64, i64, i64, C.POINTER(Inject), vp, vp]),

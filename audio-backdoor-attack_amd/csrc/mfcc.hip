@@ -468,9 +468,11 @@ __global__ void __launch_bounds__(kThreads) stft_mel_kernel(MfccDev p, const flo
 
 __global__ void __launch_bounds__(kThreads) db_dct_kernel(MfccDev p, const float* __restrict__ ws_db,
                                                           const float* __restrict__ ws_max, InjDev inj,
-                                                          float* __restrict__ out) {
+                                                          float* __restrict__ out,
+    const int32_t* __restrict__ out_rows) {
   __shared__ float db[kTT * 256];
   const int64_t u = blockIdx.x;
+  const int64_t ou = out_rows ? (int64_t)out_rows[u] : u;  // output row (abd_mfcc_rows_f32), else the batch row
   const int t0 = blockIdx.y * kTT;
   const int nt = min(kTT, p.T - t0);
   const int nv = inj.frames ? min(max(inj.frames[u], 0), p.T) : p.T;
@@ -495,7 +497,7 @@ __global__ void __launch_bounds__(kThreads) db_dct_kernel(MfccDev p, const float
     const int tt = t0 + t;
     if (pois && tt >= inj.pt0 && tt < inj.pt1 && c >= inj.pc0 && c < inj.pc1) acc = inj.pval;
     if (tt >= nv) acc = inj.fpad;
-    out[((int64_t)u * p.T + tt) * p.n_mfcc + c] = acc;
+    out[(ou * p.T + tt) * p.n_mfcc + c] = acc;
   }
 }
 
@@ -504,12 +506,14 @@ __global__ void __launch_bounds__(kThreads) db_dct_kernel(MfccDev p, const float
 constexpr int kTT2 = 16;  // frames per db_dct_lds block (52 measured equal: 0.039 ms at B = 512, 100 frames)
 __global__ void __launch_bounds__(kThreads) db_dct_lds_kernel(MfccDev p, const float* __restrict__ ws_db,
                                                               const float* __restrict__ ws_max, InjDev inj,
-                                                              float* __restrict__ out) {
+                                                              float* __restrict__ out,
+    const int32_t* __restrict__ out_rows) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* dct = sm;                           // n_mels x n_mfcc (row-major, n_mfcc % 4 == 0)
   float* db = sm + p.n_mels * p.n_mfcc;      // kTT2 x n_mels
   __shared__ float red[kThreads / kWave];
   const int64_t u = blockIdx.x;
+  const int64_t ou = out_rows ? (int64_t)out_rows[u] : u;  // output row (abd_mfcc_rows_f32), else the batch row
   const int t0 = blockIdx.y * kTT2;
   const int nt = min(kTT2, p.T - t0);
   const int nv = inj.frames ? min(max(inj.frames[u], 0), p.T) : p.T;
@@ -551,7 +555,7 @@ __global__ void __launch_bounds__(kThreads) db_dct_lds_kernel(MfccDev p, const f
         if (c0 + q >= inj.pc0 && c0 + q < inj.pc1) a[q] = inj.pval;
     }
     if (tt >= nv) acc = make_float4(inj.fpad, inj.fpad, inj.fpad, inj.fpad);
-    *reinterpret_cast<float4*>(out + ((int64_t)u * p.T + tt) * p.n_mfcc + c0) = acc;
+    *reinterpret_cast<float4*>(out + (ou * p.T + tt) * p.n_mfcc + c0) = acc;
   }
 }
 
@@ -565,9 +569,11 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 template <int NT>
 __global__ void __launch_bounds__(kThreads) db_dct_mfma_kernel(MfccDev p, const float* __restrict__ ws_db,
                                                                const float* __restrict__ ws_max, InjDev inj,
-                                                               float* __restrict__ out) {
+                                                               float* __restrict__ out,
+    const int32_t* __restrict__ out_rows) {
   __shared__ float red[kThreads / kWave];
   const int64_t u = blockIdx.x;
+  const int64_t ou = out_rows ? (int64_t)out_rows[u] : u;  // output row (abd_mfcc_rows_f32), else the batch row
   const int nv = inj.frames ? min(max(inj.frames[u], 0), p.T) : p.T;
   float mx = -INFINITY;
   if (nv < p.T) {
@@ -617,7 +623,7 @@ __global__ void __launch_bounds__(kThreads) db_dct_mfma_kernel(MfccDev p, const 
         float v = acc[n][i];
         if (pois && t >= inj.pt0 && t < inj.pt1 && c >= inj.pc0 && c < inj.pc1) v = inj.pval;
         if (t >= nv) v = inj.fpad;
-        out[((int64_t)u * p.T + t) * p.n_mfcc + c] = v;
+        out[(ou * p.T + t) * p.n_mfcc + c] = v;
       }
     }
   }
@@ -2684,6 +2690,12 @@ static int check_inj(const InjDev& r) {
 int abd_mfcc_f32(const abd_mfcc_plan* plan, const float* wave, int64_t row_stride, const int32_t* rows,
                  int64_t batch, const abd_inject* inj, float* out, void* workspace, size_t workspace_bytes,
                  abd_stream_t stream) {
+  return abd_mfcc_rows_f32(plan, wave, row_stride, rows, batch, inj, out, nullptr, workspace, workspace_bytes, stream);
+}
+
+int abd_mfcc_rows_f32(const abd_mfcc_plan* plan, const float* wave, int64_t row_stride, const int32_t* rows,
+                      int64_t batch, const abd_inject* inj, float* out, const int32_t* out_rows, void* workspace,
+                      size_t workspace_bytes, abd_stream_t stream) {
   ABD_CHECK(batch >= 0, ABD_E_INVALID, "negative batch");
   if (batch == 0) return ABD_OK;
   ABD_CHECK(plan && wave && out, ABD_E_INVALID, "NULL argument");
@@ -2738,18 +2750,48 @@ int abd_mfcc_f32(const abd_mfcc_plan* plan, const float* wave, int64_t row_strid
   const size_t dct_lds = ((size_t)d.n_mels * d.n_mfcc + (size_t)kTT2 * d.n_mels) * sizeof(float);
   if (d.dct_tiles > 0) {
     const dim3 g((unsigned)batch, (unsigned)((d.T + 63) / 64));
-    if (d.dct_tiles == 1) db_dct_mfma_kernel<1><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out);
-    else if (d.dct_tiles == 2) db_dct_mfma_kernel<2><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out);
-    else db_dct_mfma_kernel<3><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out);
+    if (d.dct_tiles == 1) db_dct_mfma_kernel<1><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out, out_rows);
+    else if (d.dct_tiles == 2) db_dct_mfma_kernel<2><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out, out_rows);
+    else db_dct_mfma_kernel<3><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out, out_rows);
   } else if (d.n_mfcc % 4 == 0 && dct_lds <= 64 * 1024 &&
-      (reinterpret_cast<uintptr_t>(out) & 15) == 0 && d.dct_lds) {
+      (reinterpret_cast<uintptr_t>(out) & 15) == 0 && d.dct_lds) {  // rows are T * n_mfcc floats: 16 B apart too
     db_dct_lds_kernel<<<dim3((unsigned)batch, (unsigned)((d.T + kTT2 - 1) / kTT2)), dim3(kThreads), dct_lds, s>>>(
-        d, ws_db, ws_max, ij, out);
+        d, ws_db, ws_max, ij, out, out_rows);
   } else {
     db_dct_kernel<<<dim3((unsigned)batch, (unsigned)((d.T + kTT - 1) / kTT)), dim3(kThreads), 0, s>>>(d, ws_db, ws_max,
-                                                                                                     ij, out);
+                                                                                                     ij, out, out_rows);
   }
   abd::prof_end(abd::PH_DB_DCT, s);
+  ABD_LAUNCH_CHECK();
+  return ABD_OK;
+}
+
+// out[u] = table[rows[u]]: block items of kThreads float4 inside one row, grid-stride over the items
+__global__ void __launch_bounds__(kThreads) gather_rows_kernel(const float4* __restrict__ table, int64_t row_vec,
+                                                               int64_t chunks, const int32_t* __restrict__ rows,
+                                                               int64_t items, float4* __restrict__ out) {
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+    const int64_t u = it / chunks;
+    const int64_t k = (it - u * chunks) * kThreads + threadIdx.x;
+    if (k < row_vec) out[u * row_vec + k] = table[(int64_t)rows[u] * row_vec + k];
+  }
+}
+
+int abd_gather_rows_f32(const float* table, int64_t row_elems, const int32_t* rows, int64_t n, float* out,
+                        abd_stream_t stream) {
+  ABD_CHECK(n >= 0 && row_elems > 0, ABD_E_INVALID, "negative row count or empty rows");
+  if (n == 0) return ABD_OK;
+  ABD_CHECK(table && rows && out, ABD_E_INVALID, "NULL argument");
+  ABD_CHECK(row_elems % 4 == 0 && ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+            ABD_E_UNSUPPORTED, "rows of %lld floats (or their buffers) are not 16-byte multiples", (long long)row_elems);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t row_vec = row_elems / 4;
+  const int64_t chunks = (row_vec + kThreads - 1) / kThreads;
+  const int64_t items = n * chunks;  // one block of float4 per item: the grid follows the bytes moved, capped
+  abd::prof_begin(abd::PH_FEAT_GATHER, s);
+  gather_rows_kernel<<<dim3((unsigned)std::min<int64_t>(items, 4096)), dim3(kThreads), 0, s>>>(
+      reinterpret_cast<const float4*>(table), row_vec, chunks, rows, items, reinterpret_cast<float4*>(out));
+  abd::prof_end(abd::PH_FEAT_GATHER, s);
   ABD_LAUNCH_CHECK();
   return ABD_OK;
 }

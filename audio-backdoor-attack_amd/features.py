@@ -140,8 +140,13 @@ class Injection:
 
 def mfcc_batch(waves: torch.Tensor, cfg: MfccConfig, rows: torch.Tensor | None = None,
                inject: Injection | None = None, out: torch.Tensor | None = None,
-               batch: int | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+               batch: int | None = None, workspace: torch.Tensor | None = None,
+               out_rows: torch.Tensor | None = None) -> torch.Tensor:
     """waves (N, >=L) fp32 on device -> (B, 1, T, n_mfcc); rows (int32, B) gathers the batch.
+
+    ``out_rows`` (int32, B, distinct, each < out.shape[0]) writes batch row u at ``out[out_rows[u]]``
+    instead of ``out[u]``: ``out`` is then a table of at least max(out_rows) + 1 rows (the resident
+    trainer's feature cache) and is returned as given.
 
     ``workspace`` (uint8, >= ``plan.workspace_bytes(B)``) is caller-owned scratch; the caller
     orders its reuse (the resident trainer keeps one per stream).  Without it each call takes a
@@ -163,11 +168,39 @@ def mfcc_batch(waves: torch.Tensor, cfg: MfccConfig, rows: torch.Tensor | None =
         assert workspace.dtype == torch.uint8 and workspace.is_cuda and workspace.numel() >= plan.workspace_bytes(B)
         ws = workspace
     inj = inject.to_c() if inject is not None else None
+    if out_rows is not None:
+        L.require_device(out, "out")
+        assert out_rows.dtype == torch.int32 and out_rows.is_cuda and out_rows.numel() == B
+        assert out.dtype == torch.float32 and out[0].numel() == plan.n_frames * cfg.n_mfcc
+        rc = L.lib().abd_mfcc_rows_f32(plan._h, waves.data_ptr(), waves.stride(0),
+                                      rows.data_ptr() if rows is not None else None, B,
+                                      C.byref(inj) if inj is not None else None, out.data_ptr(), out_rows.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), L.stream_ptr(waves.device))
+        L.check(rc, "abd_mfcc_rows_f32")
+        return out
     rc = L.lib().abd_mfcc_f32(plan._h, waves.data_ptr(), waves.stride(0),
                              rows.data_ptr() if rows is not None else None, B,
                              C.byref(inj) if inj is not None else None, out.data_ptr(),
                              ws.data_ptr(), ws.numel(), L.stream_ptr(waves.device))
     L.check(rc, "abd_mfcc_f32")
+    return out
+
+
+def gather_rows(table: torch.Tensor, rows: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[u] = table[rows[u]] (libabd abd_gather_rows_f32): table (N, ...) fp32 on device, rows int32
+    (n,) with values < N, repeats allowed; out (n, ...) of the table's row shape."""
+    L.require_device(table, "table")
+    assert table.dtype == torch.float32 and table.dim() >= 2
+    assert rows.dtype == torch.int32 and rows.is_cuda and rows.dim() == 1 and rows.is_contiguous()
+    n = rows.numel()
+    if out is None:
+        out = torch.empty((n,) + tuple(table.shape[1:]), dtype=torch.float32, device=table.device)
+    else:
+        L.require_device(out, "out")
+        assert out.dtype == torch.float32 and tuple(out.shape) == (n,) + tuple(table.shape[1:])
+    rc = L.lib().abd_gather_rows_f32(table.data_ptr(), table[0].numel(), rows.data_ptr(), n, out.data_ptr(),
+                                    L.stream_ptr(table.device))
+    L.check(rc, "abd_gather_rows_f32")
     return out
 
 

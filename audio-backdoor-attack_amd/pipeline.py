@@ -10,7 +10,11 @@ HBM and every step runs
     -> Adam -> device-side loss/acc/ASR counters
 
 with no host round trip.  The MFCC of a clip is deterministic, so training sees
-exactly the features the reference caches.
+exactly the features the reference caches -- and, like the reference, computes them
+once: with ``feature_cache`` (the default) each table row's (1, T, C) block stays in
+HBM after the first step that needs it, that step's feature stage writing it straight
+into the table (abd_mfcc_rows_f32), and every step gathers its batch from the table
+(abd_gather_rows_f32).  From the second epoch on a step's feature stage is that gather.
 
 Data parallelism (one process per GPU, torch.distributed over RCCL): every rank
 draws the same epoch permutation and takes its contiguous share of each global
@@ -154,6 +158,33 @@ class LoaderOrder:
         return torch.randperm(self.n, generator=g)
 
 
+def plan_misses(rows_np: np.ndarray, cached: np.ndarray, batch_bounds) -> list:
+    """The feature-cache misses of one epoch, planned on the host.
+
+    rows_np: the epoch's table rows in visiting order (the cache keys); cached: bool per table row,
+    read only; batch_bounds: one (start, end) slice of rows_np per step -- this rank's shard of
+    that step's global batch.  Returns, per step, the ascending positions in rows_np (start <= p <
+    end) whose row is neither cached nor planned by an earlier step (or earlier in the same step):
+    the rows that step has to compute.  A row is planned at most once, so a plan never writes one
+    cache row twice."""
+    seen = cached.copy()
+    out = []
+    for s, e in batch_bounds:
+        r = rows_np[s:e]
+        idx = np.flatnonzero(~seen[r])
+        if idx.size:
+            _, first = np.unique(r[idx], return_index=True)
+            idx = idx[np.sort(first)]
+            seen[r[idx]] = True
+        out.append((s + idx).astype(np.int64))
+    return out
+
+
+# feature_cache: the largest share of the free HBM (torch.cuda.mem_get_info at construction) the
+# (table_rows, 1, T, C) fp32 table may take; above it the trainer warns once and runs uncached
+FEATURE_CACHE_FRACTION = 0.5
+
+
 class ResidentTrainer:
     """One rank's view of HBM-resident poisoned training (see module docstring)."""
 
@@ -161,8 +192,12 @@ class ResidentTrainer:
                  optimizer: torch.optim.Optimizer, batch_size: int, trigger: np.ndarray | None = None,
                  seed: int = 35, rank: int = 0, world: int = 1, process_group=None,
                  gemm_precision: str | None = None, sync_bn: bool = False, poison_rows=None,
-                 collectives: bool | None = None):
-        """batch_size is per rank (global batch = batch_size * world).  poison_rows: explicit
+                 collectives: bool | None = None, feature_cache: bool = True,
+                 feature_cache_fraction: float | None = None):
+        """batch_size is per rank (global batch = batch_size * world).  feature_cache: keep every
+        table row's MFCC in HBM once it has been computed (the reference computes each clip's
+        features once, offline): a step computes only the rows it has not seen and gathers its
+        batch from the table; False recomputes every batch.  poison_rows: explicit
         poisoned rows (e.g. DABA's file-level schedule); default: the reference's own index work
         (poison_schedule).  sync_bn: BatchNorm statistics over the global batch (world > 1).
         collectives: run the data-parallel step (overlapped gradient all-reduce, SyncBN, separate
@@ -229,6 +264,27 @@ class ResidentTrainer:
         self.x = torch.empty((self.B, 1, self.T, cfg.n_mfcc), dtype=torch.float32, device=self.dev)
         # the feature stage's scratch, owned by this trainer and used on its one stream only
         self.feat_ws = self.plan.workspace(self.B)
+        # feature cache: one (1, T, C) block per TABLE row (JingleBack's appended styled rows
+        # included), keyed by the row a batch gathers; `cached` lives on the host, where the epoch
+        # permutation is drawn, so an epoch's misses are planned without asking the device
+        self.fcache = None
+        self.cached = None
+        self._fcache_key = None
+        self._miss = None
+        self._step_k = 0
+        self._src_row_np = self.src_row.cpu().numpy() if self.src_row is not None else None
+        if feature_cache:
+            frac = FEATURE_CACHE_FRACTION if feature_cache_fraction is None else float(feature_cache_fraction)
+            rows_t = int(self.waves.shape[0])
+            need = rows_t * self.T * cfg.n_mfcc * 4
+            free = torch.cuda.mem_get_info(self.dev)[0]
+            if need > frac * free:
+                import warnings
+                warnings.warn(f"feature cache disabled: {need / 2**20:.0f} MiB for {rows_t} rows exceeds "
+                              f"{frac:g} of the {free / 2**20:.0f} MiB of free HBM; recomputing MFCC every step")
+            else:
+                self.fcache = torch.empty((rows_t, 1, self.T, cfg.n_mfcc), dtype=torch.float32, device=self.dev)
+                self.cached = np.zeros(rows_t, dtype=bool)
         self.metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=self.dev)
         model.train()
         if gemm_precision is not None:
@@ -256,11 +312,55 @@ class ResidentTrainer:
 
     # -------------------------------------------------------------- epoch plumbing
     def new_epoch(self):
-        perm = self.order.next_epoch().to(self.dev)
+        perm_host = self.order.next_epoch()
+        perm = perm_host.to(self.dev)
         rows = self.src_row[perm] if self.src_row is not None else perm.to(torch.int32)
         self._epoch = (rows, self.eff_labels[perm], self.ind[perm], self.poison[perm],
                        self.position[perm] if self.position is not None else None)
         self._pos = 0
+        if self.fcache is not None:
+            p = perm_host.numpy()
+            self._rows_np = self._src_row_np[p] if self._src_row_np is not None else p
+            self._bounds, pos = [], 0
+            while self._batch_rows(pos) is not None:
+                g = self._batch_rows(pos)
+                self._bounds.append(DP.shard_range(pos, g, self.rank, self.world))
+                pos += g
+            self._cache_validate()
+            self._plan_cache(0)
+
+    # -------------------------------------------------------------- feature cache
+    def _cache_validate(self):
+        """Forget every cached row if the wave table or the trigger was rewritten (the key of
+        _row_scale_key); True if it was."""
+        key = (self.waves.data_ptr(), self.waves._version) + \
+            ((self.trigger.data_ptr(), self.trigger._version) if self.trigger is not None else ())
+        if key == self._fcache_key:
+            return False
+        self.cached[:] = False
+        self._fcache_key = key
+        return True
+
+    def _plan_cache(self, k0):
+        """Plan the misses of steps k0.. of the current epoch from `cached` (plan_misses) and upload
+        all their positions at once: self._miss[k] = (rows, poison, position, rows on the host) of
+        step k's misses, None for a step that only gathers."""
+        miss = plan_misses(self._rows_np, self.cached, self._bounds[k0:])
+        self._miss = [None] * len(self._bounds)
+        if sum(m.size for m in miss) == 0:
+            return
+        idx = torch.from_numpy(np.concatenate(miss))
+        idx = idx.pin_memory().to(self.dev, non_blocking=True)
+        rows, _, _, pois, pos = self._epoch
+        m_rows, m_pois = rows[idx], pois[idx]
+        m_pos = pos[idx] if pos is not None else None
+        a = 0
+        for k, m in enumerate(miss, k0):
+            if m.size:
+                b = a + m.size
+                self._miss[k] = (m_rows[a:b], m_pois[a:b], m_pos[a:b] if m_pos is not None else None,
+                                 self._rows_np[m])
+                a = b
 
     def _batch_rows(self, pos):
         """Rows of the global batch starting at pos: a full B * world, or the loader's short last
@@ -289,6 +389,7 @@ class ResidentTrainer:
         rows, lab, ind, pois, pos = self._epoch
         s, e = DP.shard_range(self._pos, g, self.rank, self.world)
         self._cur = (g, s - self._pos)   # (global rows, global row of this rank's first row)
+        self._step_k = self._pos // (self.B * self.world)   # step of the epoch (feature-cache plan)
         self._pos += g
         return rows[s:e], lab[s:e], ind[s:e], pois[s:e], pos[s:e] if pos is not None else None
 
@@ -301,9 +402,25 @@ class ResidentTrainer:
                                               F.Injection(mode=self.cfg.inject_mode, trigger=self.trigger,
                                                           snr_db=self.cfg.snr_db))
                 self._row_scale_key = key
-        inj = F.Injection(mode=self.cfg.inject_mode, trigger=self.trigger, poison=pois, position=pos,
-                          snr_db=self.cfg.snr_db, patch=self.cfg.patch, row_scale=self.row_scale)
-        F.mfcc_batch(self.waves, self.mcfg, rows=rows, inject=inj, out=out, workspace=self.feat_ws)
+        if self.fcache is None:
+            inj = F.Injection(mode=self.cfg.inject_mode, trigger=self.trigger, poison=pois, position=pos,
+                              snr_db=self.cfg.snr_db, patch=self.cfg.patch, row_scale=self.row_scale)
+            F.mfcc_batch(self.waves, self.mcfg, rows=rows, inject=inj, out=out, workspace=self.feat_ws)
+            return
+        # cached path: the rows this step has not seen go through the feature stage straight into
+        # their cache rows (out_rows), then the whole batch is gathered from the table on the same
+        # stream -- partial hits (tail batches, another rank's rows, a refill) need nothing more
+        if self._cache_validate():
+            self._plan_cache(self._step_k)
+        miss = self._miss[self._step_k]
+        if miss is not None:
+            m_rows, m_pois, m_pos, m_rows_np = miss
+            inj = F.Injection(mode=self.cfg.inject_mode, trigger=self.trigger, poison=m_pois, position=m_pos,
+                              snr_db=self.cfg.snr_db, patch=self.cfg.patch, row_scale=self.row_scale)
+            F.mfcc_batch(self.waves, self.mcfg, rows=m_rows, inject=inj, out=self.fcache, out_rows=m_rows,
+                         workspace=self.feat_ws)
+            self.cached[m_rows_np] = True
+        F.gather_rows(self.fcache, rows, out=out)
 
     def step(self):
         """One global batch: this rank's share through inject -> MFCC -> train step [-> all-reduce] -> Adam."""

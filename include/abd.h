@@ -102,6 +102,22 @@ int abd_mfcc_f32(const abd_mfcc_plan* plan, const float* wave, int64_t row_strid
                  const int32_t* rows, int64_t batch, const abd_inject* inj, float* out,
                  void* workspace, size_t workspace_bytes, abd_stream_t stream);
 
+/* abd_mfcc_f32 with an output-row indirection: batch row u's (T, n_mfcc) block is written at
+ * out + out_rows[u] * T * n_mfcc (int32[batch], distinct rows; NULL = u, i.e. abd_mfcc_f32), so a
+ * batch lands directly in the rows of a larger table -- the resident trainer's feature cache, keyed
+ * by the wave-table row.  rows, inj->poison / position / frames stay indexed by the batch row. */
+int abd_mfcc_rows_f32(const abd_mfcc_plan* plan, const float* wave, int64_t row_stride,
+                      const int32_t* rows, int64_t batch, const abd_inject* inj, float* out,
+                      const int32_t* out_rows, void* workspace, size_t workspace_bytes,
+                      abd_stream_t stream);
+
+/* out[u] = table[rows[u]] for u < n: rows of row_elems floats (row_elems * 4 B a multiple of 16, both
+ * buffers 16-byte aligned, else ABD_E_UNSUPPORTED), moved as 16-byte vectors with 64-bit offsets;
+ * rows may repeat; n = 0 launches nothing.  The feature cache's per-step read: the batch's cached
+ * (T, n_mfcc) blocks into the model input. */
+int abd_gather_rows_f32(const float* table, int64_t row_elems, const int32_t* rows, int64_t n,
+                        float* out, abd_stream_t stream);
+
 /* The injected waveform itself (batch, length): the reference's bd_*_wav arrays
  * (ultrasonic.py:75, flowmur.py:85/106). */
 int abd_inject_waveform_f32(const float* wave, int64_t row_stride, int64_t length,
