@@ -29,6 +29,7 @@ EXPORTS = (
     "abd_smallcnn_train_step",
     "abd_smallcnn_apply", "abd_smallcnn_forward", "abd_smallcnn_backward", "abd_smallcnn_eval", "abd_adam_f32",
     "abd_smallcnn_input_grad_workspace_bytes", "abd_smallcnn_input_grad",
+    "abd_smallcnn_ablate_workspace_bytes", "abd_smallcnn_ablate_eval",
     "abd_profile_start", "abd_profile_start_every", "abd_profile_step", "abd_profile_stop",
 )
 
@@ -63,6 +64,9 @@ class Effect(C.Structure):
 FX_GAIN, FX_DISTORTION, FX_LADDER, FX_PHASER, FX_CHORUS, FX_REVERB, FX_PITCHSHIFT = 0, 1, 2, 3, 4, 5, 6
 PREC_F32, PREC_BF16, PREC_F32_SPLIT = 0, 1, 2
 PRECISIONS = {"f32": PREC_F32, "bf16": PREC_BF16, "f32split": PREC_F32_SPLIT}
+ABLATE_CONV_FILTER, ABLATE_BN_WEIGHT = 0, 1
+ABLATE_KINDS = {"conv": ABLATE_CONV_FILTER, "bn": ABLATE_BN_WEIGHT}
+ABLATE_CHANNELS = 160   # mask columns: conv1 0..63, conv2 64..127, conv3 128..159
 
 
 class TrainArgs(C.Structure):
@@ -144,6 +148,8 @@ def _declare(lib):
         "abd_adam_f32": (i32, [vp, vp, vp, vp, i64, i64, f32, f32, f32, f32, vp]),
         "abd_smallcnn_input_grad_workspace_bytes": (sz, [vp, i64]),
         "abd_smallcnn_input_grad": (i32, [vp, vp, i64, vp, vp, vp, f32, vp, vp, vp, vp, sz, vp]),
+        "abd_smallcnn_ablate_workspace_bytes": (sz, [vp, i64, i32]),
+        "abd_smallcnn_ablate_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
         "abd_profile_start": (i32, [C.c_ulonglong, i32]),
         "abd_profile_start_every": (i32, [C.c_ulonglong, i32, i32]),
         "abd_profile_step": (i32, []),

@@ -5,6 +5,8 @@
     torch.ops.abd.inject_waveform      ultrasonic.py:75, flowmur.py:77-85 / 101-106
     torch.ops.abd.smallcnn_eval        utils/models.py:43-65 in eval mode
     torch.ops.abd.smallcnn_eval_metrics  the same + test()'s counters (utils/training_tools.py:98-128)
+    torch.ops.abd.smallcnn_ablate_eval the defenses' neuron-ablation scan (ft_reg.py:173-190), all variants
+                                       of a batch in one launch sequence
     torch.ops.abd.smallcnn_train_step  utils/training_tools.py:60-79: forward, CE, backward, Adam,
                                        loss / accuracy / ASR counters -- one launch sequence
     torch.ops.abd.adam                 torch.optim.Adam single-tensor step (flat buffers)
@@ -132,6 +134,45 @@ def smallcnn_eval_metrics(x: Tensor, params: Tensor, running: Tensor, num_classe
 @smallcnn_eval_metrics.register_fake
 def _(x, params, running, num_classes, precision, labels, indicators, metrics):
     return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::smallcnn_ablate_eval", mutates_args=("loss_sum", "correct"))
+def smallcnn_ablate_eval(x: Tensor, params: Tensor, running: Tensor, labels: Tensor, masks: Tensor, kind: int,
+                         variants_per_pass: int, loss_sum: Tensor, correct: Tensor, num_classes: int,
+                         precision: str = "f32split") -> None:
+    """The neuron-ablation sweep on one batch (abd_smallcnn_ablate_eval): variant v is the eval model with
+    the conv filters (kind 0) or BN weights (kind 1) of masks[v] zeroed; loss_sum[v] (float64) += the batch's
+    summed CE loss, correct[v] (int64) += its correct predictions.  masks is a (V, 160) uint8 HOST tensor
+    (conv1 0..63, conv2 64..127, conv3 128..159); a device tensor is copied to the host first."""
+    L.require_device(x, "smallcnn input")
+    for t, what in ((params, "params"), (running, "running"), (labels, "labels"), (loss_sum, "loss_sum"),
+                    (correct, "correct")):
+        L.require_device(t, what)
+    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    m = masks.detach().to("cpu", torch.uint8).contiguous()
+    V = int(m.shape[0])
+    if m.dim() != 2 or m.shape[1] != L.ABLATE_CHANNELS:
+        raise L.AbdError(f"masks must be (V, {L.ABLATE_CHANNELS}), got {tuple(m.shape)}")
+    if loss_sum.numel() < V or correct.numel() < V or loss_sum.dtype != torch.float64 or correct.dtype != torch.int64:
+        raise L.AbdError("loss_sum (float64) and correct (int64) need one entry per variant")
+    if labels.dtype != torch.int64 or labels.numel() != B:
+        raise L.AbdError("labels must be int64, one per batch row")
+    if B == 0 or V == 0:
+        return None
+    h = _net(H0, W0, num_classes, precision)
+    vpp = max(1, min(int(variants_per_pass), V))
+    ws = _ws(L.lib().abd_smallcnn_ablate_workspace_bytes(h, B, vpp), x.device)
+    L.check(L.lib().abd_smallcnn_ablate_eval(h, x.data_ptr(), B, params.data_ptr(), running.data_ptr(),
+                                             labels.data_ptr(), m.data_ptr(), V, int(kind), vpp, loss_sum.data_ptr(),
+                                             correct.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
+            "abd_smallcnn_ablate_eval")
+    return None
+
+
+@smallcnn_ablate_eval.register_fake
+def _(x, params, running, labels, masks, kind, variants_per_pass, loss_sum, correct, num_classes,
+      precision="f32split"):
+    return None
 
 
 @torch.library.custom_op("abd::smallcnn_train_step",

@@ -372,6 +372,35 @@ int abd_smallcnn_eval(abd_cnn* net, const float* x, int64_t batch, const float* 
                       const int64_t* indicators, float* logprobs, int64_t* metrics,
                       void* workspace, size_t workspace_bytes, abd_stream_t stream);
 
+/* Batched neuron-ablation sweep: the defenses' loss-change scan (ft_reg.py:173-190 prune_one_neuron +
+ * get_loss_change; :163-171 pruning and tsbd.py:43-47 zero_reinit_toget with a set of filters per
+ * variant).  Variant v is the model with the parameters its mask row selects set to zero --
+ * conv<i>.weight[c] = 0 (ABD_ABLATE_CONV_FILTER) or bn<i>.weight[c] = 0 (ABD_ABLATE_BN_WEIGHT,
+ * --layer_type bn) -- run as model.eval() on the batch with nn.CrossEntropyLoss on the log-probs.
+ * The parameters are never patched: an ablated channel's pooled activation is one constant, the next
+ * conv's pre-activation differs from the baseline's by a rank-1 term, and (variant, row) pairs run
+ * through the eval kernels as one virtual batch.  Per call each layer is computed at most once for
+ * all variants whose earliest ablated layer lies after it; a variant costs only the layers behind
+ * its earliest ablated one.
+ *   masks   HOST memory, (n_variants, 160) bytes, nonzero = ablated: conv1 channels 0..63, conv2
+ *           64..127, conv3 128..159.  Any mask: empty (the baseline), several channels in several
+ *           layers, a whole layer.  Read before the call returns; it reaches the device as kernel
+ *           arguments, so the launch sequence stays capture-safe.
+ *   loss_sum[v] += sum over the batch rows of the CE loss (double), correct[v] += rows whose arg-max
+ *           is the label (int64): device buffers of n_variants entries that accumulate over calls.
+ *   variants_per_pass  variants evaluated together inside the workspace (any n_variants, the tail
+ *           pass included); variants_per_pass * batch rows must keep the layer-3 kernels' 32-bit
+ *           offsets (else ABD_E_INVALID).
+ * batch == 0 or n_variants == 0 launches nothing.  ABD_PREC_F32 / ABD_PREC_F32_SPLIT only.
+ * workspace: abd_smallcnn_ablate_workspace_bytes(net, batch, variants_per_pass). */
+enum { ABD_ABLATE_CONV_FILTER = 0, ABD_ABLATE_BN_WEIGHT = 1 };
+size_t abd_smallcnn_ablate_workspace_bytes(const abd_cnn* net, int64_t batch, int variants_per_pass);
+int abd_smallcnn_ablate_eval(abd_cnn* net, const float* x, int64_t batch, const float* params,
+                             const float* running, const int64_t* labels, const uint8_t* masks,
+                             int n_variants, int kind, int variants_per_pass, double* loss_sum,
+                             int64_t* correct, void* workspace, size_t workspace_bytes,
+                             abd_stream_t stream);
+
 /* Frozen-model input gradient (utils/flowmur_generate_trigger.py:98-103: the benign model,
  * saved by EarlyStoppingModel right after clean_test() and therefore in eval mode, with
  * requires_grad off): eval forward (running BN statistics, no dropout), CrossEntropyLoss on
