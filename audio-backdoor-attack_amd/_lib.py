@@ -30,6 +30,8 @@ EXPORTS = (
     "abd_smallcnn_apply", "abd_smallcnn_forward", "abd_smallcnn_backward", "abd_smallcnn_eval", "abd_adam_f32",
     "abd_smallcnn_input_grad_workspace_bytes", "abd_smallcnn_input_grad",
     "abd_smallcnn_ablate_workspace_bytes", "abd_smallcnn_ablate_eval",
+    "abd_segment_norms_workspace_bytes", "abd_segment_norms_f32", "abd_perturb_f32", "abd_sgd_f32",
+    "abd_smallcnn_finetune_reg_workspace_bytes", "abd_smallcnn_finetune_reg_step",
     "abd_profile_start", "abd_profile_start_every", "abd_profile_step", "abd_profile_stop",
 )
 
@@ -82,6 +84,23 @@ class TrainArgs(C.Structure):
         ("fc_grads_event", C.c_void_p), ("row_offset", C.c_int64),
         ("bn_sync_buf", C.c_void_p), ("bn_sync", C.c_void_p), ("bn_sync_ctx", C.c_void_p),
     ]
+
+
+class FinetuneRegArgs(C.Structure):
+    """abd_finetune_reg_args: one batch of train_finetuning_reg (ft_reg.py:83-123)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("labels", C.c_void_p), ("batch", C.c_int64),
+        ("params", C.c_void_p), ("grads", C.c_void_p), ("running", C.c_void_p), ("num_batches_tracked", C.c_void_p),
+        ("seed", C.c_uint64), ("counter", C.c_uint64), ("row_offset", C.c_int64),
+        ("r", C.c_float), ("alpha", C.c_float), ("lr", C.c_float), ("momentum", C.c_float),
+        ("momentum_buf", C.c_void_p),
+        ("mask1_in", C.c_void_p * 3), ("mask2_in", C.c_void_p * 3),
+        ("mask1_out", C.c_void_p * 3), ("mask2_out", C.c_void_p * 3),
+        ("logprobs_out", C.c_void_p), ("loss_sum", C.c_void_p), ("correct", C.c_void_p),
+    ]
+
+
+MAX_SEGMENTS = 32
 
 
 # int (*bn_sync)(void* ctx, int point, int64_t offset, int64_t n)  (abd_train_args.bn_sync)
@@ -150,6 +169,12 @@ def _declare(lib):
         "abd_smallcnn_input_grad": (i32, [vp, vp, i64, vp, vp, vp, f32, vp, vp, vp, vp, sz, vp]),
         "abd_smallcnn_ablate_workspace_bytes": (sz, [vp, i64, i32]),
         "abd_smallcnn_ablate_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
+        "abd_segment_norms_workspace_bytes": (sz, [C.POINTER(i64), i32]),
+        "abd_segment_norms_f32": (i32, [vp, C.POINTER(i64), i32, vp, vp, sz, vp]),
+        "abd_perturb_f32": (i32, [vp, vp, vp, C.POINTER(i64), i32, f32, vp, vp]),
+        "abd_sgd_f32": (i32, [vp, vp, vp, f32, vp, f32, f32, vp, i64, vp]),
+        "abd_smallcnn_finetune_reg_workspace_bytes": (sz, [vp, i64]),
+        "abd_smallcnn_finetune_reg_step": (i32, [vp, C.POINTER(FinetuneRegArgs), vp, sz, vp]),
         "abd_profile_start": (i32, [C.c_ulonglong, i32]),
         "abd_profile_start_every": (i32, [C.c_ulonglong, i32, i32]),
         "abd_profile_step": (i32, []),

@@ -4,6 +4,8 @@
     ft_reg.py:125-139         temp_test (loss = mean of batch means)   -> ablation_sweep
     ft_reg.py:173-190         prune_one_neuron + get_loss_change       -> neuron_loss_change
     ft_reg.py:163-171,338-343 pruning() ratio scan, tsbd.py:43-47      -> pruned_eval
+    ft_reg.py:83-123          train_finetuning_reg                     -> finetune_reg_epoch
+    ft_reg.py:57-81, tsbd.py:140-161  train_finetuning                 -> finetune_epoch
 
 The reference deep-copies the model per neuron, zeroes ``state_dict[layer][idx]`` and runs a whole
 DataLoader pass: 160 evaluations per set.  Here every batch is evaluated once for all variants
@@ -161,3 +163,119 @@ def pruned_eval(model, x, y, ranked_names, ratios, batch_size=256):
     masks, kind = pack_masks([ranked_names[:int(r * len(ranked_names))] for r in ratios])
     loss, acc = ablation_sweep(model, x, y, masks, kind, batch_size)
     return loss.numpy(), acc.numpy()
+
+
+# ------------------------------------------------------------------ fine-tuning (ft_reg.py:57-123)
+def epoch_order(n: int, order):
+    """The epoch's row permutation as a host int64 array, or None for sequential order.  It must be a
+    permutation of 0..n-1 (a shuffled DataLoader visits every row once)."""
+    if order is None:
+        return None
+    o = torch.as_tensor(order).detach().cpu().numpy() if not isinstance(order, np.ndarray) else order
+    if o.ndim != 1 or o.dtype.kind not in "iu":
+        raise ValueError("order must be a 1-D integer row permutation")
+    o = o.astype(np.int64)
+    if len(o) != n or not np.array_equal(np.sort(o), np.arange(n)):
+        raise ValueError(f"order must be a permutation of 0..{n - 1}")
+    return o
+
+
+def _epoch_batches(x, y, batch_size, order):
+    """[(x_b, y_b)] device batches in the epoch's order: views when sequential, gathers under a permutation."""
+    N = int(x.shape[0])
+    o = epoch_order(N, order)
+    y = y.to(torch.int64)
+    bounds = batch_bounds(N, int(batch_size))
+    if o is None:
+        return [(x[s:e], y[s:e]) for s, e in bounds]
+    idx = torch.from_numpy(o).to(x.device)
+    return [(x.index_select(0, idx[s:e]), y.index_select(0, idx[s:e])) for s, e in bounds]
+
+
+def _check_finetune_inputs(model, x, y, what):
+    from .models import smallcnn
+    L.require_device(x, f"{what} input")
+    L.require_device(y, f"{what} labels")
+    if not isinstance(model, smallcnn):
+        raise L.AbdError(f"{what} runs the abd_amd smallcnn only, got {type(model).__name__}")
+    if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32 or y.numel() != x.shape[0]:
+        raise ValueError(f"{what} expects x (N, 1, T, n_mfcc) float32 and one label per row")
+    if x.shape[0] == 0:
+        raise ValueError(f"{what} needs at least one row")
+
+
+def final_gradients(model):
+    """``p.grad``-style views of the engine's flat gradient buffer, in parameter order; also installed as
+    the parameters' .grad (the reference assigns ``param.grad = grad``, ft_reg.py:110-112)."""
+    from . import training as T
+    T.expose_grads(model)
+    return [p.grad for p in model._param_list()]
+
+
+def finetune_reg_epoch(model, x, y, optimizer, r, alpha, batch_size=256, order=None):
+    """One epoch of train_finetuning_reg (ft_reg.py:83-123).  x (N, 1, T, n_mfcc) float32 and y (N) are
+    device-resident; order is the epoch's row permutation (default: sequential).  optimizer is a
+    torch.optim.SGD over the model's parameters (training.SgdBinding).  Every batch is one
+    torch.ops.abd.smallcnn_finetune_reg_step: the model is updated in place through its engine and never
+    copied.  Returns (loss, acc, final_gradients): the sum of the post-update batch-mean losses over the
+    number of batches, correct predictions over samples, and views of the last batch's blended gradient."""
+    from . import ops, training as T  # noqa: F401  (registers torch.ops.abd)
+    from .models import dropout_seed
+    _check_finetune_inputs(model, x, y, "finetune_reg_epoch")
+    T.check_sgd(model, optimizer)
+    model.train()
+    dev = x.device
+    eng = model.engine(x)
+    sgd = T.SgdBinding(model, optimizer)
+    loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
+    correct = torch.zeros(1, dtype=torch.int64, device=dev)
+    batches = _epoch_batches(x, y, batch_size, order)
+    for xb, yb in batches:
+        B = int(xb.shape[0])
+        m1 = m2 = None
+        hm = [model.step_masks(B, dev) for _ in range(3)]   # 'torch_cpu' dropout source: one draw per forward
+        if hm[0] is not None:
+            m1, m2 = torch.stack([h[0] for h in hm]), torch.stack([h[1] for h in hm])
+        torch.ops.abd.smallcnn_finetune_reg_step(
+            xb.contiguous(), yb.contiguous(), eng.params, eng.grads, sgd.buf, eng.running, eng.nbt, loss_sum, correct,
+            eng.K, float(r), float(alpha), sgd.lr, sgd.momentum, dropout_seed(dev, model), model._step, None, None, m1,
+            m2, model.gemm_precision)
+        model._step += 3
+    loss = float(loss_sum.item()) / len(batches)
+    acc = float(correct.item()) / int(x.shape[0])
+    return loss, acc, final_gradients(model)
+
+
+def finetune_epoch(model, x, y, optimizer, batch_size=256, order=None):
+    """One epoch of the plain train_finetuning (ft_reg.py:57-81, tsbd.py:140-161) on device-resident
+    (x, y): torch.optim.SGD (with or without momentum; a no-update train step, then abd::sgd) or
+    torch.optim.Adam (the fused train step).  Returns (loss, acc) like the reference: the sum of the
+    batch-mean losses of each step's own pre-update forward over the number of batches, and correct
+    predictions over samples (a fraction, not a percentage)."""
+    from . import ops, training as T  # noqa: F401  (registers torch.ops.abd)
+    _check_finetune_inputs(model, x, y, "finetune_epoch")
+    adam = isinstance(optimizer, torch.optim.Adam)
+    if adam:
+        if not T.fusable(model, optimizer, torch.nn.CrossEntropyLoss()):
+            raise L.AbdError("finetune_epoch: this Adam configuration is not the fused step's (one param group over "
+                             "the model's parameters, no weight decay / amsgrad / maximize)")
+    else:
+        T.check_sgd(model, optimizer)
+    model.train()
+    dev = x.device
+    eng = model.engine(x)
+    bind = T.AdamBinding(model, optimizer) if adam else T.SgdBinding(model, optimizer)
+    metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
+    batches = _epoch_batches(x, y, batch_size, order)
+    for xb, yb in batches:
+        xb, yb = xb.contiguous(), yb.contiguous()
+        if adam:
+            T.op_train_step(model, xb, yb, None, bind, metrics)
+        else:
+            T.train_step(model, xb, yb, None, None, metrics, do_update=False)
+            torch.ops.abd.sgd(eng.params, eng.grads, bind.buf, None, bind.lr, bind.momentum)
+    if adam:
+        bind.sync_torch_state()
+    T.expose_grads(model)
+    loss_sum, total, hit, _, _, _ = T.read_metrics(metrics)
+    return loss_sum / len(batches), hit / total

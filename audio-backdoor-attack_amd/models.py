@@ -61,6 +61,7 @@ class _Engine:
         self.grads = torch.zeros(self.n, dtype=torch.float32, device=device)
         self.exp_avg = None
         self.exp_avg_sq = None
+        self.momentum_buf = None   # flat SGD momentum buffer (training.SgdBinding)
         self.running = torch.empty(320, dtype=torch.float32, device=device)
         self.nbt = torch.zeros(3, dtype=torch.int64, device=device)
         self._ws = None

@@ -10,6 +10,10 @@
     torch.ops.abd.smallcnn_train_step  utils/training_tools.py:60-79: forward, CE, backward, Adam,
                                        loss / accuracy / ASR counters -- one launch sequence
     torch.ops.abd.adam                 torch.optim.Adam single-tensor step (flat buffers)
+    torch.ops.abd.sgd                  torch.optim.SGD with momentum (flat buffers; optional two-gradient blend)
+    torch.ops.abd.segment_norms / perturb  per-tensor ``grad.norm()`` and ``param += r * grad / norm`` (ft_reg.py:99-101)
+    torch.ops.abd.smallcnn_finetune_reg_step  ft_reg.py:83-123: one batch of train_finetuning_reg -- two gradient
+                                       passes, the displaced parameters, SGD, the loss / accuracy forward
 
 Each op enqueues its HIP kernels on the current torch stream through the C ABI
 (include/abd.h) and has a fake (meta) implementation, so the ops trace under FakeTensor /
@@ -230,3 +234,138 @@ def adam(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, ste
 @adam.register_fake
 def _(params, grads, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps):
     return None
+
+
+# --------------------------------------------------------------------------- fine-tuning (ft_reg.py)
+def _offsets(offsets):
+    """Segment offsets as the C ABI's host int64 array (validated by the library)."""
+    offs = [int(o) for o in offsets]
+    if len(offs) < 2:
+        raise L.AbdError("segment offsets need at least two entries")
+    return (C.c_int64 * len(offs))(*offs), len(offs) - 1
+
+
+@torch.library.custom_op("abd::segment_norms", mutates_args=())
+def segment_norms(buf: Tensor, offsets: list[int]) -> Tensor:
+    """L2 norm of each segment [offsets[s], offsets[s + 1]) of a flat fp32 buffer: double accumulation in a
+    fixed order, rounded to fp32 once (``grad.norm()`` per parameter tensor, ft_reg.py:101)."""
+    L.require_device(buf, "segment_norms buffer")
+    if buf.dtype != torch.float32:
+        raise L.AbdError("segment_norms expects float32")
+    arr, n_seg = _offsets(offsets)
+    if offsets[-1] > buf.numel():
+        raise L.AbdError("segment offsets reach past the buffer")
+    out = torch.empty(n_seg, dtype=torch.float32, device=buf.device)
+    ws = _ws(max(L.lib().abd_segment_norms_workspace_bytes(arr, n_seg), 8), buf.device)
+    L.check(L.lib().abd_segment_norms_f32(buf.data_ptr(), arr, n_seg, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          L.stream_ptr(buf.device)), "abd_segment_norms_f32")
+    return out
+
+
+@segment_norms.register_fake
+def _(buf, offsets):
+    return buf.new_empty((len(offsets) - 1,))
+
+
+@torch.library.custom_op("abd::perturb", mutates_args=())
+def perturb(params: Tensor, grads: Tensor, norms: Tensor, offsets: list[int], r: float) -> Tensor:
+    """out = params + r * (grads / norms[segment]) in fp32, a new flat tensor (ft_reg.py:99-101 on a copy);
+    elements outside [offsets[0], offsets[-1]) are copied.  A zero norm gives NaN in its segment."""
+    for t, what in ((params, "params"), (grads, "grads"), (norms, "norms")):
+        L.require_device(t, what)
+    arr, n_seg = _offsets(offsets)
+    if offsets[-1] > params.numel() or grads.numel() != params.numel() or norms.numel() < n_seg:
+        raise L.AbdError("perturb: segment offsets / buffer sizes do not agree")
+    out = params.clone()
+    L.check(L.lib().abd_perturb_f32(params.data_ptr(), grads.data_ptr(), norms.data_ptr(), arr, n_seg, float(r),
+                                    out.data_ptr(), L.stream_ptr(params.device)), "abd_perturb_f32")
+    return out
+
+
+@perturb.register_fake
+def _(params, grads, norms, offsets, r):
+    return torch.empty_like(params)
+
+
+@torch.library.custom_op("abd::sgd", mutates_args=("params", "momentum_buf", "grad_out"))
+def sgd(params: Tensor, grads: Tensor, momentum_buf: Optional[Tensor], grad_out: Optional[Tensor], lr: float,
+        momentum: float = 0.0, grads2: Optional[Tensor] = None, alpha: float = 0.0) -> None:
+    """torch.optim.SGD single-tensor update over flat fp32 buffers (dampening 0, no Nesterov, weight_decay 0):
+    d = grads, or (1 - alpha) grads + alpha grads2; momentum_buf = momentum * momentum_buf + d;
+    params -= lr * momentum_buf.  momentum_buf None is plain SGD (momentum must be 0).  grad_out (or None)
+    receives d.  (The mutated arguments carry no defaults: torch's in-place bookkeeping indexes them by position.)"""
+    L.require_device(params, "params")
+    n = params.numel()
+    for t, what in ((grads, "grads"), (momentum_buf, "momentum_buf"), (grads2, "grads2"), (grad_out, "grad_out")):
+        if t is not None:
+            L.require_device(t, what)
+            if t.numel() != n or t.dtype != torch.float32:
+                raise L.AbdError(f"sgd: {what} must be float32 with params' element count")
+    L.check(L.lib().abd_sgd_f32(params.data_ptr(), grads.data_ptr(), _ptr(grads2), float(alpha), _ptr(momentum_buf),
+                                float(momentum), float(lr), _ptr(grad_out), n, L.stream_ptr(params.device)),
+            "abd_sgd_f32")
+    return None
+
+
+@sgd.register_fake
+def _(params, grads, momentum_buf, grad_out, lr, momentum=0.0, grads2=None, alpha=0.0):
+    return None
+
+
+@torch.library.custom_op("abd::smallcnn_finetune_reg_step",
+                         mutates_args=("params", "grads", "momentum_buf", "running", "num_batches_tracked", "loss_sum",
+                                       "correct", "mask1_out", "mask2_out"))
+def smallcnn_finetune_reg_step(x: Tensor, labels: Tensor, params: Tensor, grads: Tensor,
+                               momentum_buf: Optional[Tensor], running: Tensor, num_batches_tracked: Tensor,
+                               loss_sum: Tensor, correct: Tensor, num_classes: int, r: float, alpha: float, lr: float,
+                               momentum: float, seed: int, counter: int, mask1_out: Optional[Tensor],
+                               mask2_out: Optional[Tensor], mask1_in: Optional[Tensor] = None,
+                               mask2_in: Optional[Tensor] = None, precision: str = "f32split",
+                               row_offset: int = 0) -> Tensor:
+    """One batch of train_finetuning_reg (ft_reg.py:83-123) on the device; returns the log-probs of its three
+    forwards (3, B, K).  params, momentum_buf, running and num_batches_tracked are updated in place, grads is
+    left holding (1 - alpha) g1 + alpha g2, loss_sum (float64[1]) += the post-update batch-mean loss, correct
+    (int64[1]) += its hits.  mask*_in / mask*_out are (3, B, flat) and (3, B, 128) uint8, one slice per forward;
+    without mask*_in the masks come from (seed, counter), (seed, counter + 1), (seed, counter + 2)."""
+    L.require_device(x, "smallcnn input")
+    for t, what in ((labels, "labels"), (params, "params"), (grads, "grads"), (running, "running"),
+                    (num_batches_tracked, "num_batches_tracked"), (loss_sum, "loss_sum"), (correct, "correct")):
+        L.require_device(t, what)
+    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    h = _net(H0, W0, num_classes, precision)
+    flat = L.lib().abd_smallcnn_flat_features(h)
+    if labels.dtype != torch.int64 or labels.numel() != B:
+        raise L.AbdError("labels must be int64, one per batch row")
+    if loss_sum.dtype != torch.float64 or correct.dtype != torch.int64 or not loss_sum.numel() or not correct.numel():
+        raise L.AbdError("loss_sum (float64) and correct (int64) need one entry each")
+    if (mask1_in is None) != (mask2_in is None) or (mask1_out is None) != (mask2_out is None):
+        raise L.AbdError("dropout masks come in pairs")
+    a = L.FinetuneRegArgs()
+    for m, cols, what in ((mask1_in, flat, "mask1_in"), (mask2_in, 128, "mask2_in"), (mask1_out, flat, "mask1_out"),
+                          (mask2_out, 128, "mask2_out")):
+        if m is None:
+            continue
+        L.require_device(m, what)
+        if m.dtype != torch.uint8 or tuple(m.shape) != (3, B, cols):
+            raise L.AbdError(f"{what} must be uint8 (3, {B}, {cols}), got {tuple(m.shape)}")
+        for k in range(3):
+            getattr(a, what)[k] = m.data_ptr() + k * B * cols
+    out = torch.empty((3, B, int(num_classes)), dtype=torch.float32, device=x.device)
+    a.x, a.labels, a.batch = x.data_ptr(), labels.data_ptr(), B
+    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
+    a.num_batches_tracked = num_batches_tracked.data_ptr()
+    a.seed, a.counter, a.row_offset = int(seed), int(counter), int(row_offset)
+    a.r, a.alpha, a.lr, a.momentum = float(r), float(alpha), float(lr), float(momentum)
+    a.momentum_buf = _ptr(momentum_buf)
+    a.logprobs_out, a.loss_sum, a.correct = out.data_ptr(), loss_sum.data_ptr(), correct.data_ptr()
+    ws = _ws(L.lib().abd_smallcnn_finetune_reg_workspace_bytes(h, B), x.device)
+    L.check(L.lib().abd_smallcnn_finetune_reg_step(h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
+            "abd_smallcnn_finetune_reg_step")
+    return out
+
+
+@smallcnn_finetune_reg_step.register_fake
+def _(x, labels, params, grads, momentum_buf, running, num_batches_tracked, loss_sum, correct, num_classes, r, alpha,
+      lr, momentum, seed, counter, mask1_out, mask2_out, mask1_in=None, mask2_in=None, precision="f32split",
+      row_offset=0):
+    return x.new_empty((3, x.shape[0], num_classes))

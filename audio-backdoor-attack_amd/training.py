@@ -54,6 +54,51 @@ class AdamBinding:
             self.opt.state[p]["step"].fill_(float(self.step))
 
 
+class SgdBinding:
+    """torch.optim.SGD(momentum) for the device fine-tuning steps (defense.finetune_epoch /
+    finetune_reg_epoch): one flat momentum buffer whose per-parameter views are installed as
+    ``optimizer.state[p]["momentum_buffer"]``, so a later plain ``optimizer.step()`` continues from it.
+    A zero buffer reproduces torch's first step (buf = grad) exactly.  Only what abd::sgd computes is
+    accepted: one param group over exactly the model's parameters, dampening 0, no Nesterov, no weight
+    decay, no maximize; anything else raises AbdError."""
+
+    def __init__(self, model: smallcnn, optimizer: torch.optim.Optimizer):
+        check_sgd(model, optimizer)
+        eng = model._engine
+        if eng is None:
+            raise L.AbdError("SgdBinding needs a model bound to the device (model.engine(x)) first")
+        self.model, self.opt = model, optimizer
+        g = optimizer.param_groups[0]
+        self.lr, self.momentum = float(g["lr"]), float(g["momentum"])
+        self.buf = None
+        if self.momentum != 0.0:
+            if getattr(eng, "momentum_buf", None) is None:
+                eng.momentum_buf = torch.zeros_like(eng.params)
+            self.buf = eng.momentum_buf
+            for p, bv in zip(model._param_list(), eng.views(self.buf)):
+                st = optimizer.state[p]
+                old = st.get("momentum_buffer")
+                if old is not None and old.data_ptr() != bv.data_ptr():
+                    bv.copy_(old.reshape(-1))
+                st["momentum_buffer"] = bv.view(p.shape)
+
+
+def check_sgd(model, optimizer):
+    """Raise AbdError unless optimizer is an SGD that abd::sgd reproduces (see SgdBinding)."""
+    if not isinstance(model, smallcnn):
+        _unsupported(model)
+    if not isinstance(optimizer, torch.optim.SGD):
+        raise L.AbdError(f"expected torch.optim.SGD, got {type(optimizer).__name__}")
+    if len(optimizer.param_groups) != 1:
+        raise L.AbdError("abd::sgd supports one param group (the layer-wise-lr optimizer of ft_reg.py is never stepped)")
+    g = optimizer.param_groups[0]
+    for key, ok in (("nesterov", False), ("dampening", 0), ("weight_decay", 0), ("maximize", False)):
+        if g.get(key, ok) != ok:
+            raise L.AbdError(f"abd::sgd does not implement {key}={g[key]!r}")
+    if [id(p) for p in g["params"]] != [id(p) for p in model.parameters()]:
+        raise L.AbdError("the optimizer must hold exactly the model's parameters, in order")
+
+
 def fusable(model, optimizer, criterion) -> bool:
     if not isinstance(model, smallcnn) or not isinstance(optimizer, torch.optim.Adam):
         return False

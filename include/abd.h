@@ -418,6 +418,83 @@ int abd_adam_f32(float* params, const float* grads, float* exp_avg, float* exp_a
                  int64_t n, int64_t step, float lr, float beta1, float beta2, float eps,
                  abd_stream_t stream);
 
+/* ------------------------------------------------------------------ regularised fine-tuning
+ * Replaces ft_reg.py:83-123 train_finetuning_reg (one batch: gradient g1 at the parameters, every
+ * parameter tensor moved by r * g1 / ||g1||, gradient g2 at the moved point, torch.optim.SGD with
+ * momentum on (1 - alpha) g1 + alpha g2, a train-mode forward for loss / accuracy) and the plain
+ * train_finetuning of ft_reg.py:57-81 / tsbd.py:140-161 (SGD with momentum).  The reference
+ * deep-copies the model per batch; here the displaced parameters live in the workspace.
+ *
+ * Segments: `offsets` is HOST memory, n_seg + 1 ascending int64 element offsets into the flat fp32
+ * buffers (abd_smallcnn_param_offsets() gives the model's 16 tensors); segment s is
+ * [offsets[s], offsets[s + 1]).  1 <= n_seg <= ABD_MAX_SEGMENTS and no segment may be empty, else
+ * ABD_E_INVALID.  The offsets are read before the call returns and reach the device as kernel
+ * arguments.  Every reduction runs in a fixed order (no floating-point atomics): equal inputs give
+ * bit-equal results. */
+#define ABD_MAX_SEGMENTS 32
+
+/* norms[s] = ||buf[offsets[s] : offsets[s + 1]]||_2 (device float[n_seg]): squares accumulated in
+ * double (per-block partial sums in the workspace, then one fixed-order sum per segment), sqrt in
+ * double, rounded to fp32 once.  buf needs only its natural 4-byte alignment. */
+size_t abd_segment_norms_workspace_bytes(const int64_t* offsets, int n_seg);
+int abd_segment_norms_f32(const float* buf, const int64_t* offsets, int n_seg, float* norms,
+                          void* workspace, size_t workspace_bytes, abd_stream_t stream);
+
+/* out[i] = p[i] + r * (g[i] / norms[seg(i)]) for offsets[0] <= i < offsets[n_seg], each operation
+ * rounded to fp32 in that order: ft_reg.py:101 ``param.data += r * (grad / grad.norm())``.  out may
+ * not alias p or g (ABD_E_INVALID when out == p or out == g).  A zero norm gives NaN (0 / 0) in
+ * every element of that segment, as the reference does; it is not guarded. */
+int abd_perturb_f32(const float* p, const float* g, const float* norms, const int64_t* offsets,
+                    int n_seg, float r, float* out, abd_stream_t stream);
+
+/* torch.optim.SGD single-tensor step over flat buffers (dampening 0, no Nesterov, weight_decay 0):
+ *     d = g                                  (g2 == NULL)
+ *     d = (1 - alpha) * g + alpha * g2       (g2 != NULL: ft_reg.py:109 final_gradients)
+ *     buf = momentum * buf + d ; p -= lr * buf          (buf != NULL)
+ *     p -= lr * d                                        (buf == NULL, requires momentum == 0)
+ * A zero-initialised buf reproduces torch's first step (buf = d) exactly, so there is no step index.
+ * grad_out (optional) receives d; it may alias g or g2. */
+int abd_sgd_f32(float* p, const float* g, const float* g2, float alpha, float* buf, float momentum,
+                float lr, float* grad_out, int64_t n, abd_stream_t stream);
+
+/* One batch of train_finetuning_reg on the device.  Forward k (0, 1, 2) takes its dropout keep masks
+ * from mask1_in[k] / mask2_in[k] ((B, flat) / (B, 128) bytes; NULL = generated from (seed,
+ * counter + k)) and reports the masks it used in mask1_out[k] / mask2_out[k] (optional).
+ *   1. train step without update at params -> g1; its BN running statistics go to a scratch copy
+ *   2. per-tensor norms of g1, perturbed parameters into the workspace
+ *   3. train step without update at the perturbed parameters, same batch, scratch statistics -> g2
+ *   4. abd_sgd_f32 on params with (g1, g2, alpha); the blended gradient is left in grads
+ *   5. train-mode forward at the updated params with the real running / num_batches_tracked, which
+ *      therefore advance exactly once per batch (the reference's forwards 1 and 2 run on the
+ *      discarded copy)
+ *   6. *loss_sum += the batch-mean CrossEntropyLoss of forward 5's log-probs (double),
+ *      *correct += its arg-max hits
+ * The net's GEMM precision applies to all three passes.  batch >= 1.
+ * workspace: abd_smallcnn_finetune_reg_workspace_bytes(net, batch). */
+typedef struct abd_finetune_reg_args {
+  const float* x;               /* (B,1,H0,W0)                                        */
+  const int64_t* labels;        /* (B)                                                */
+  int64_t batch;
+  float* params;                /* flat, updated in place                             */
+  float* grads;                 /* flat (written): (1 - alpha) g1 + alpha g2          */
+  float* running;               /* 6 BN buffers packed like abd_train_args.running    */
+  int64_t* num_batches_tracked; /* optional int64[3], += 1                            */
+  uint64_t seed, counter;
+  int64_t row_offset;
+  float r, alpha, lr, momentum;
+  float* momentum_buf;          /* flat; NULL requires momentum == 0                  */
+  const uint8_t* mask1_in[3];
+  const uint8_t* mask2_in[3];
+  uint8_t* mask1_out[3];
+  uint8_t* mask2_out[3];
+  float* logprobs_out;          /* optional (3, B, K): the log-probs of the 3 forwards */
+  double* loss_sum;             /* device accumulators                                */
+  int64_t* correct;
+} abd_finetune_reg_args;
+size_t abd_smallcnn_finetune_reg_workspace_bytes(const abd_cnn* net, int64_t batch);
+int abd_smallcnn_finetune_reg_step(abd_cnn* net, const abd_finetune_reg_args* a, void* workspace,
+                                   size_t workspace_bytes, abd_stream_t stream);
+
 /* ------------------------------------------------------------------ profiling
  * Per-phase HIP-event brackets around libabd launches (bench.py roofline).  Bit i of
  * phase_mask enables phase i (see csrc/prof.h: 0 stft_mel, 1 db_dct, 6 conv2 fwd,
