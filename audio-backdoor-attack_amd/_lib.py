@@ -32,6 +32,8 @@ EXPORTS = (
     "abd_smallcnn_ablate_workspace_bytes", "abd_smallcnn_ablate_eval",
     "abd_segment_norms_workspace_bytes", "abd_segment_norms_f32", "abd_perturb_f32", "abd_sgd_f32",
     "abd_smallcnn_finetune_reg_workspace_bytes", "abd_smallcnn_finetune_reg_step",
+    "abd_row_abs_sums_f32", "abd_smallcnn_unlearn_workspace_bytes", "abd_smallcnn_unlearn_step",
+    "abd_reinit_weights_f32",
     "abd_profile_start", "abd_profile_start_every", "abd_profile_step", "abd_profile_stop",
 )
 
@@ -101,6 +103,30 @@ class FinetuneRegArgs(C.Structure):
 
 
 MAX_SEGMENTS = 32
+
+
+class RowSegment(C.Structure):
+    """abd_row_segment: `rows` rows of `row_len` floats from element `offset` of a flat buffer."""
+    _fields_ = [("offset", C.c_int64), ("rows", C.c_int64), ("row_len", C.c_int64)]
+
+
+class UnlearnArgs(C.Structure):
+    """abd_unlearn_args: one batch of train_unlearning (tsbd.py:108-138)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("labels", C.c_void_p), ("batch", C.c_int64),
+        ("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("running", C.c_void_p), ("num_batches_tracked", C.c_void_p),
+        ("adam_step", C.c_int64), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("seed", C.c_uint64), ("counter", C.c_uint64), ("row_offset", C.c_int64),
+        ("mask1_in", C.c_void_p), ("mask2_in", C.c_void_p), ("mask1_out", C.c_void_p), ("mask2_out", C.c_void_p),
+        ("logprobs_out", C.c_void_p), ("metrics", C.c_void_p),
+        ("record_offset", C.c_int64), ("record_rows", C.c_int64), ("record_row_len", C.c_int64),
+        ("record_abs_sums", C.c_void_p),
+    ]
+
+
+MAX_REINIT_VARIANTS = 16
+MAX_REINIT_ROWS = 1024
 
 
 # int (*bn_sync)(void* ctx, int point, int64_t offset, int64_t n)  (abd_train_args.bn_sync)
@@ -175,6 +201,11 @@ def _declare(lib):
         "abd_sgd_f32": (i32, [vp, vp, vp, f32, vp, f32, f32, vp, i64, vp]),
         "abd_smallcnn_finetune_reg_workspace_bytes": (sz, [vp, i64]),
         "abd_smallcnn_finetune_reg_step": (i32, [vp, C.POINTER(FinetuneRegArgs), vp, sz, vp]),
+        "abd_row_abs_sums_f32": (i32, [vp, vp, C.POINTER(RowSegment), i32, vp, vp, vp]),
+        "abd_smallcnn_unlearn_workspace_bytes": (sz, [vp, i64]),
+        "abd_smallcnn_unlearn_step": (i32, [vp, C.POINTER(UnlearnArgs), vp, sz, vp]),
+        "abd_reinit_weights_f32": (i32, [vp, i64, vp, C.POINTER(RowSegment), i32, vp, C.POINTER(i64), i32, vp, vp, vp,
+                                         vp]),
         "abd_profile_start": (i32, [C.c_ulonglong, i32]),
         "abd_profile_start_every": (i32, [C.c_ulonglong, i32, i32]),
         "abd_profile_step": (i32, []),

@@ -6,6 +6,9 @@
     ft_reg.py:163-171,338-343 pruning() ratio scan, tsbd.py:43-47      -> pruned_eval
     ft_reg.py:83-123          train_finetuning_reg                     -> finetune_reg_epoch
     ft_reg.py:57-81, tsbd.py:140-161  train_finetuning                 -> finetune_epoch
+    tsbd.py:108-138           train_unlearning                         -> unlearn_epoch
+    tsbd.py:342-367           NWC scores, ucn.txt, ranking             -> neuron_weight_change, ucn_text, rank_neurons
+    tsbd.py:49-63,371-380     zero_reinit_weight and its ratio sweep   -> reinit_models, reinit_sweep
 
 The reference deep-copies the model per neuron, zeroes ``state_dict[layer][idx]`` and runs a whole
 DataLoader pass: 160 evaluations per set.  Here every batch is evaluated once for all variants
@@ -279,3 +282,251 @@ def finetune_epoch(model, x, y, optimizer, batch_size=256, order=None):
     T.expose_grads(model)
     loss_sum, total, hit, _, _, _ = T.read_metrics(metrics)
     return loss_sum / len(batches), hit / total
+
+
+# ------------------------------------------------------------------ TSBD (tsbd.py:49-63,108-138,310-380)
+REINIT_RATIO = (0.01, 0.05, 0.1, 0.15, 0.2, 0.25, 0.3, 0.4, 0.5, 0.7, 0.9)   # tsbd.py:17 reinit_ratio
+UCN_HEAD = "No \t Layer_Name \t Neuron_Idx \t Score \n"
+
+
+def param_offsets(model):
+    """Element offsets of the 16 parameter tensors inside the flat buffers (17 entries, parameter order)."""
+    d = dict(model.named_parameters())
+    offs = [0]
+    for n in PARAM_ORDER:
+        offs.append(offs[-1] + d[n].numel())
+    return offs
+
+
+def row_table(model, layer_type="conv"):
+    """The C ABI's row table of the layer type's weights as a flat [offset, rows, row_len, ...] list:
+    conv<i>.weight as (out channels) rows of in * kh * kw weights, bn<i>.weight as rows of length 1 -- the
+    ``view(shape[0], -1)`` of tsbd.py:351 -- in get_layerName_from_type's order."""
+    if layer_type not in L.ABLATE_KINDS:
+        raise SystemError("NO valid layer_type match!")   # the reference's own error
+    offs = param_offsets(model)
+    d = dict(model.named_parameters())
+    table = []
+    for s, _, _ in LAYERS:
+        name = f"{layer_type}{s}.weight"
+        p = d[name]
+        table += [offs[PARAM_ORDER.index(name)], int(p.shape[0]), int(p.numel() // p.shape[0])]
+    return table
+
+
+def _adam_binding(model, optimizer, what):
+    from . import training as T
+    if not T.fusable(model, optimizer, torch.nn.CrossEntropyLoss()):
+        raise L.AbdError(f"{what}: this optimizer is not the device Adam step's (torch.optim.Adam, one param group "
+                         "over the model's parameters, no weight decay / amsgrad / maximize)")
+    return T.AdamBinding(model, optimizer)
+
+
+def unlearn_epoch(model, x, y, optimizer, record_layer="conv3.weight", batch_size=256, order=None, whole_epoch=False):
+    """One call of train_unlearning (tsbd.py:108-138, correlation_analysis.py:41-71) on device-resident
+    (x, y): gradient ascent on the CrossEntropyLoss with torch.optim.Adam, one
+    torch.ops.abd.smallcnn_unlearn_step per batch.  Returns (loss, acc, avg_gradNorm, var_gradNorm).
+
+    The reference's ``return`` sits inside its batch loop: every call trains on the FIRST batch only, yet
+    divides the loss by the number of batches and the hits by the size of the whole set, and the variance
+    of its single gradient-norm row is NaN.  That is the default here.  whole_epoch=True visits every
+    batch (the loop the reference presumably meant), same divisors, mean / unbiased variance over the
+    batches' rows.  record_layer None records nothing (correlation_analysis.py's variant): the two
+    gradient-norm results are then None.  The parameters' .grad are views of the last batch's gradient
+    of -loss, as ``(-loss).backward()`` leaves them."""
+    from . import ops, training as T  # noqa: F401  (registers torch.ops.abd)
+    from .models import dropout_seed
+    _check_finetune_inputs(model, x, y, "unlearn_epoch")
+    model.train()
+    dev = x.device
+    eng = model.engine(x)
+    adam = _adam_binding(model, optimizer, "unlearn_epoch")
+    record = None
+    if record_layer is not None:
+        d = dict(model.named_parameters())
+        if record_layer not in PARAM_ORDER:
+            raise ValueError(f"record_layer {record_layer!r} is not a smallcnn parameter")
+        p = d[record_layer]
+        record = [eng.offsets[PARAM_ORDER.index(record_layer)], int(p.shape[0]), int(p.numel() // p.shape[0])]
+    batches = _epoch_batches(x, y, batch_size, order)
+    metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
+    norms = []
+    for xb, yb in batches if whole_epoch else batches[:1]:
+        hm = model.step_masks(int(xb.shape[0]), dev)
+        row = torch.empty(record[1], dtype=torch.float32, device=dev) if record else None
+        adam.step += 1
+        torch.ops.abd.smallcnn_unlearn_step(
+            xb.contiguous(), yb.contiguous(), eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, eng.running, eng.nbt,
+            metrics, row, None, None, eng.K, adam.step, adam.lr, adam.betas[0], adam.betas[1], adam.eps,
+            dropout_seed(dev, model), model._step, record, hm[0] if hm is not None else None,
+            hm[1] if hm is not None else None, model.gemm_precision)
+        model._step += 1
+        norms.append(row)
+    adam.sync_torch_state()
+    T.expose_grads(model)
+    loss_sum, _, hit, _, _, _ = T.read_metrics(metrics)
+    loss, acc = loss_sum / len(batches), float(hit) / int(x.shape[0])
+    if record is None:
+        return loss, acc, None, None
+    stack = torch.stack(norms, 0).float()
+    return loss, acc, stack.mean(dim=0), stack.var(dim=0)
+
+
+def _flat_params(src, device):
+    """A model, a state dict or a flat tensor -> the flat fp32 parameter buffer on the device."""
+    if torch.is_tensor(src):
+        return src.detach().reshape(-1).to(device, torch.float32).contiguous()
+    sd = src.state_dict() if hasattr(src, "state_dict") else src
+    return torch.cat([torch.as_tensor(sd[k]).detach().reshape(-1).to(device, torch.float32) for k in PARAM_ORDER])
+
+
+def neuron_weight_change(model, original_params, layer_type="conv"):
+    """The NWC of tsbd.py:342-363 / correlation_analysis.get_neuron_weight_change: (names, scores, absdiff).
+    original_params: the backdoored model before unlearning (a model, a state dict or a flat parameter
+    tensor).  names 'conv1.weight.0' ...; scores[i] = sum |p_unlearned - p_original| over neuron i's weights
+    (float32 numpy: double accumulation rounded once); absdiff the per-weight changes themselves, the rows of
+    all neurons packed in name order, a float32 DEVICE tensor (the reference's n2w_dict values, absdiff_rows)."""
+    from . import ops  # noqa: F401  (registers torch.ops.abd)
+    eng = getattr(model, "_engine", None)
+    if eng is None:
+        raise L.AbdError("neuron_weight_change needs a model bound to the device (it has no CPU path)")
+    params, _ = _flat_state(model, eng.device)
+    orig = _flat_params(original_params, eng.device)
+    if orig.numel() != params.numel():
+        raise ValueError("original_params does not hold this model's parameters")
+    absdiff, sums = torch.ops.abd.row_abs_sums(params.contiguous(), orig, row_table(model, layer_type))
+    return neuron_names(model, layer_type), sums.cpu().numpy(), absdiff
+
+
+def absdiff_rows(model, absdiff, layer_type="conv"):
+    """{neuron name: list of its per-weight changes}: the reference's n2w_dict (tsbd.py:356) from packed rows."""
+    table = row_table(model, layer_type)
+    names = neuron_names(model, layer_type)
+    host = torch.as_tensor(absdiff).detach().cpu()
+    out, at, i = {}, 0, 0
+    for rows, n in zip(table[1::3], table[2::3]):
+        for _ in range(rows):
+            out[names[i]] = host[at:at + n].tolist()
+            at += n
+            i += 1
+    return out
+
+
+def ucn_text(names, scores):
+    """The text of the reference's ucn.txt (tsbd.py:357-361): header, then one
+    '{} \\t {} \\t {} \\t {:.4f} \\n' line per neuron.  Readable by the reference's read_data."""
+    lines = [UCN_HEAD]
+    for i, (name, s) in enumerate(zip(names, scores)):
+        layer, idx = name.rsplit(".", 1)
+        lines.append("{} \t {} \t {} \t {:.4f} \n".format(i, layer, idx, float(s)))
+    return "".join(lines)
+
+
+def rank_neurons(text_or_scores):
+    """read_data + sorted(key=float(value), reverse=True) (tsbd.py:65-71,366-367): [(layer_name, idx, value)],
+    descending by the 4-decimal value of the text, ties in file order (a stable sort).  Takes the ucn text, or
+    (names, scores), which go through ucn_text first -- the ranking always sees the rounded values."""
+    text = text_or_scores if isinstance(text_or_scores, str) else ucn_text(*text_or_scores)
+    rows = []
+    for line in text.splitlines()[1:]:
+        f = line.split()
+        if not f:
+            continue
+        if len(f) != 4:
+            raise ValueError(f"not a ucn line: {line!r}")
+        rows.append((f[1], int(f[2]), float(f[3])))
+    return sorted(rows, key=lambda r: float(r[2]), reverse=True)
+
+
+def _ranked_layer_type(ranked):
+    kinds = {mask_column(f"{layer}.{idx}")[0] for layer, idx, _ in ranked}
+    if len(kinds) != 1:
+        raise ValueError("a ranking holds conv filters or bn weights, not both (and not nothing)")
+    return kinds.pop()
+
+
+def reinit_selection(model, ranked, ratios, wratio):
+    """(table, row_select (V, rows) uint8, k [V], layer_type) of zero_reinit_weight for each ratio:
+    top_num = int(len(ranked) * ratio) neurons selected, k = int(m * wratio) of their m weights.  Raises
+    ValueError where the reference's ``min([])`` does (top_num == 0 or k == 0)."""
+    ranked = list(ranked)
+    lt = _ranked_layer_type(ranked)
+    table = row_table(model, lt)
+    names = neuron_names(model, lt)
+    row_of = {n: i for i, n in enumerate(names)}
+    row_len = [n for rows, n in zip(table[1::3], table[2::3]) for _ in range(rows)]
+    sel = np.zeros((len(ratios), len(names)), np.uint8)
+    ks = []
+    for v, ratio in enumerate(ratios):
+        top_num = int(len(ranked) * ratio)
+        for layer, idx, _ in ranked[:top_num]:
+            sel[v, row_of[f"{layer}.{int(idx)}"]] = 1
+        m = int(sum(row_len[r] for r in np.nonzero(sel[v])[0]))
+        k = int(m * wratio)
+        if top_num == 0 or k == 0:
+            raise ValueError(f"reinit ratio {ratio}: min() arg is an empty sequence (top_num {top_num}, k {k})")
+        ks.append(k)
+    return table, sel, ks, lt
+
+
+def reinit_models(model, ranked, absdiff, ratios, wratio):
+    """zero_reinit_weight (tsbd.py:49-63) of the model for every ratio: (params (V, n_params), thr (V), zeroed
+    (V)) device tensors.  ranked: rank_neurons' list; absdiff: neuron_weight_change's packed rows.  The model
+    is read, never modified; params[v] is a flat parameter buffer for torch.ops.abd.smallcnn_eval*."""
+    from . import ops  # noqa: F401  (registers torch.ops.abd)
+    L.require_device(absdiff, "absdiff")
+    table, sel, ks, _ = reinit_selection(model, ranked, ratios, wratio)
+    params, _ = _flat_state(model, absdiff.device)
+    params = params.contiguous()
+    outs = []
+    for s in range(0, len(ks), L.MAX_REINIT_VARIANTS):
+        e = s + L.MAX_REINIT_VARIANTS
+        outs.append(torch.ops.abd.reinit_weights(params, absdiff, table, torch.from_numpy(sel[s:e]), ks[s:e]))
+    return tuple(torch.cat([o[i] for o in outs]) for i in range(3))
+
+
+def model_with_params(model, flat_params):
+    """A deep copy of the smallcnn carrying one variant's flat parameters (BN buffers and settings as the
+    model's), unbound: ready for finetune_epoch, which binds it on first use (tsbd.py:373-374,382-394)."""
+    import copy
+    new = copy.deepcopy(model)
+    flat = flat_params.detach().reshape(-1)
+    offs = param_offsets(new)
+    if flat.numel() != offs[-1]:
+        raise ValueError("flat_params does not hold this model's parameters")
+    with torch.no_grad():
+        for p, o in zip(new._param_list(), offs):
+            p.data = flat[o:o + p.numel()].to(p.device, p.dtype).reshape(p.shape).clone()
+    return new
+
+
+def reinit_sweep(model, clean_x, clean_y, bd_x, bd_y, bd_indicator, ranked, absdiff, ratios=REINIT_RATIO, wratio=0.7,
+                 batch_size=256):
+    """The re-initialisation sweep of tsbd.py:371-380: per ratio (test_clean_acc, test_asr, clean_test_loss,
+    bd_test_loss) with training.test's definitions (percentages; the losses are means over the batches of the
+    batch-mean loss).  All sets are device-resident; every variant's evaluation is abd_smallcnn_eval on its
+    row of reinit_models' parameter sets, the model itself is neither copied nor modified."""
+    from . import ops, training as T  # noqa: F401  (registers torch.ops.abd)
+    for t, what in ((clean_x, "clean input"), (clean_y, "clean labels"), (bd_x, "backdoor input"),
+                    (bd_y, "backdoor labels"), (bd_indicator, "backdoor indicator")):
+        L.require_device(t, f"reinit_sweep {what}")
+    dev = clean_x.device
+    params, _, _ = reinit_models(model, ranked, absdiff, ratios, wratio)
+    _, running = _flat_state(model, dev)
+    K = int(model.state_dict()["fc2.weight"].shape[0])
+    prec = getattr(model, "gemm_precision", "f32split")
+    clean_y, bd_y, bd_indicator = clean_y.to(torch.int64), bd_y.to(torch.int64), bd_indicator.to(torch.int64)
+    results = []
+    for v in range(len(ratios)):
+        words = []
+        for xs, ys, ind in ((clean_x, clean_y, None), (bd_x, bd_y, bd_indicator)):
+            metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
+            bounds = batch_bounds(int(xs.shape[0]), int(batch_size))
+            for s, e in bounds:
+                torch.ops.abd.smallcnn_eval_metrics(xs[s:e], params[v], running, K, prec, ys[s:e],
+                                                    ind[s:e] if ind is not None else None, metrics)
+            words.append((metrics, len(bounds)))
+        (cl, ct, cc, _, _, _), nc = T.read_metrics(words[0][0]), words[0][1]
+        (bl, _, _, pt, ah, _), nb = T.read_metrics(words[1][0]), words[1][1]
+        results.append((100 * cc / ct, 100 * ah / pt, cl / nc, bl / nb))
+    return results

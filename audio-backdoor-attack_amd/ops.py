@@ -369,3 +369,156 @@ def _(x, labels, params, grads, momentum_buf, running, num_batches_tracked, loss
       lr, momentum, seed, counter, mask1_out, mask2_out, mask1_in=None, mask2_in=None, precision="f32split",
       row_offset=0):
     return x.new_empty((3, x.shape[0], num_classes))
+
+
+# --------------------------------------------------------------------------- TSBD (tsbd.py)
+def _row_table(table):
+    """A flat list of (offset, rows, row_len) triples as the C ABI's host array (validated by the library)."""
+    vals = [int(v) for v in table]
+    if not vals or len(vals) % 3:
+        raise L.AbdError("a row table is a flat list of (offset, rows, row_len) triples")
+    n_seg = len(vals) // 3
+    arr = (L.RowSegment * n_seg)(*[L.RowSegment(*vals[3 * s:3 * s + 3]) for s in range(n_seg)])
+    return arr, n_seg, vals
+
+
+def _table_extent(vals):
+    """(total rows, packed values, one past the last element) of a row table."""
+    rows = sum(vals[1::3])
+    packed = sum(r * n for r, n in zip(vals[1::3], vals[2::3]))
+    end = max(o + r * n for o, r, n in zip(vals[0::3], vals[1::3], vals[2::3]))
+    return rows, packed, end
+
+
+@torch.library.custom_op("abd::row_abs_sums", mutates_args=())
+def row_abs_sums(a: Tensor, b: Optional[Tensor], table: list[int], want_absdiff: bool = True) -> tuple[Tensor, Tensor]:
+    """(absdiff, row_sums) of a row table (flat (offset, rows, row_len) triples) over flat fp32 buffers:
+    absdiff = (a - b).abs() (a.abs() without b) with the table's rows packed one after another, bit-equal to
+    torch's; row_sums[r] its per-row sum, double accumulation rounded to fp32 once (tsbd.py:350-352, :127).
+    want_absdiff False returns an empty absdiff."""
+    L.require_device(a, "row_abs_sums a")
+    if a.dtype != torch.float32:
+        raise L.AbdError("row_abs_sums expects float32")
+    if b is not None:
+        L.require_device(b, "row_abs_sums b")
+        if b.dtype != torch.float32 or b.numel() != a.numel():
+            raise L.AbdError("row_abs_sums: b must be float32 with a's element count")
+    arr, n_seg, vals = _row_table(table)
+    if min(vals) < 0:
+        raise L.AbdError("row table entries must not be negative")
+    rows, packed, end = _table_extent(vals)
+    if end > a.numel():
+        raise L.AbdError("row table reaches past the buffer")
+    absdiff = torch.empty(packed if want_absdiff else 0, dtype=torch.float32, device=a.device)
+    sums = torch.empty(rows, dtype=torch.float32, device=a.device)
+    L.check(L.lib().abd_row_abs_sums_f32(a.data_ptr(), _ptr(b), arr, n_seg, absdiff.data_ptr() if want_absdiff else None,
+                                         sums.data_ptr(), L.stream_ptr(a.device)), "abd_row_abs_sums_f32")
+    return absdiff, sums
+
+
+@row_abs_sums.register_fake
+def _(a, b, table, want_absdiff=True):
+    rows, packed, _ = _table_extent([int(v) for v in table])
+    return a.new_empty((packed if want_absdiff else 0,)), a.new_empty((rows,))
+
+
+@torch.library.custom_op("abd::smallcnn_unlearn_step",
+                         mutates_args=("params", "grads", "exp_avg", "exp_avg_sq", "running", "num_batches_tracked",
+                                       "metrics", "record_abs_sums", "mask1_out", "mask2_out"))
+def smallcnn_unlearn_step(x: Tensor, labels: Tensor, params: Tensor, grads: Tensor, exp_avg: Tensor,
+                          exp_avg_sq: Tensor, running: Tensor, num_batches_tracked: Tensor, metrics: Tensor,
+                          record_abs_sums: Optional[Tensor], mask1_out: Optional[Tensor], mask2_out: Optional[Tensor],
+                          num_classes: int, adam_step: int, lr: float, beta1: float, beta2: float, eps: float,
+                          seed: int, counter: int, record: Optional[list[int]] = None,
+                          mask1_in: Optional[Tensor] = None, mask2_in: Optional[Tensor] = None,
+                          precision: str = "f32split", row_offset: int = 0) -> Tensor:
+    """One batch of train_unlearning (tsbd.py:108-138) on the device; returns the batch's log-probs (B, K).
+    A no-update train step (metrics += the positive loss and the hits, BN buffers advance once), then grads
+    <- -grads and torch.optim.Adam (step index adam_step >= 1) on it.  record = [offset, rows, row_len] of the
+    record layer inside the flat buffers: record_abs_sums (float32[rows]) receives its per-row |grad| sums."""
+    L.require_device(x, "smallcnn input")
+    for t, what in ((labels, "labels"), (params, "params"), (grads, "grads"), (exp_avg, "exp_avg"),
+                    (exp_avg_sq, "exp_avg_sq"), (running, "running"), (num_batches_tracked, "num_batches_tracked"),
+                    (metrics, "metrics")):
+        L.require_device(t, what)
+    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    h = _net(H0, W0, num_classes, precision)
+    flat = L.lib().abd_smallcnn_flat_features(h)
+    if labels.dtype != torch.int64 or labels.numel() != B:
+        raise L.AbdError("labels must be int64, one per batch row")
+    if (mask1_in is None) != (mask2_in is None) or (mask1_out is None) != (mask2_out is None):
+        raise L.AbdError("dropout masks come in pairs")
+    for m, cols, what in ((mask1_in, flat, "mask1_in"), (mask2_in, 128, "mask2_in"), (mask1_out, flat, "mask1_out"),
+                          (mask2_out, 128, "mask2_out")):
+        if m is not None:
+            L.require_device(m, what)
+            if m.dtype != torch.uint8 or tuple(m.shape) != (B, cols):
+                raise L.AbdError(f"{what} must be uint8 ({B}, {cols}), got {tuple(m.shape)}")
+    a = L.UnlearnArgs()
+    if record is not None:
+        if len(record) != 3 or record_abs_sums is None:
+            raise L.AbdError("record is [offset, rows, row_len] and needs record_abs_sums")
+        L.require_device(record_abs_sums, "record_abs_sums")
+        if record_abs_sums.dtype != torch.float32 or record_abs_sums.numel() < int(record[1]):
+            raise L.AbdError("record_abs_sums must be float32 with one entry per record row")
+        a.record_offset, a.record_rows, a.record_row_len = (int(v) for v in record)
+        a.record_abs_sums = record_abs_sums.data_ptr()
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
+    a.x, a.labels, a.batch = x.data_ptr(), labels.data_ptr(), B
+    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
+    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    a.num_batches_tracked = num_batches_tracked.data_ptr()
+    a.adam_step, a.lr, a.beta1, a.beta2, a.eps = int(adam_step), float(lr), float(beta1), float(beta2), float(eps)
+    a.seed, a.counter, a.row_offset = int(seed), int(counter), int(row_offset)
+    a.mask1_in, a.mask2_in, a.mask1_out, a.mask2_out = _ptr(mask1_in), _ptr(mask2_in), _ptr(mask1_out), _ptr(mask2_out)
+    a.logprobs_out, a.metrics = out.data_ptr(), metrics.data_ptr()
+    ws = _ws(L.lib().abd_smallcnn_unlearn_workspace_bytes(h, B), x.device)
+    L.check(L.lib().abd_smallcnn_unlearn_step(h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
+            "abd_smallcnn_unlearn_step")
+    return out
+
+
+@smallcnn_unlearn_step.register_fake
+def _(x, labels, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics, record_abs_sums, mask1_out,
+      mask2_out, num_classes, adam_step, lr, beta1, beta2, eps, seed, counter, record=None, mask1_in=None,
+      mask2_in=None, precision="f32split", row_offset=0):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::reinit_weights", mutates_args=())
+def reinit_weights(params: Tensor, absdiff: Tensor, table: list[int], row_select: Tensor,
+                   k: list[int]) -> tuple[Tensor, Tensor, Tensor]:
+    """zero_reinit_weight (tsbd.py:49-63) for V variants at once: (out (V, n_params), thr (V), zeroed (V) int64).
+    absdiff: the packed rows of abd::row_abs_sums; row_select: (V, total rows) uint8 HOST tensor (a device tensor
+    is copied to the host first), nonzero = the neuron is among the variant's top_num; k[v] = int(m * wratio).
+    out[v] = params with every weight of the selected rows whose absdiff >= the k[v]-th largest set to 0."""
+    L.require_device(params, "params")
+    L.require_device(absdiff, "absdiff")
+    if params.dtype != torch.float32 or absdiff.dtype != torch.float32:
+        raise L.AbdError("reinit_weights expects float32")
+    arr, n_seg, vals = _row_table(table)
+    if min(vals) < 0:
+        raise L.AbdError("row table entries must not be negative")
+    rows, packed, end = _table_extent(vals)
+    sel = row_select.detach().to("cpu", torch.uint8).contiguous()
+    V = len(k)
+    if sel.dim() != 2 or tuple(sel.shape) != (V, rows):
+        raise L.AbdError(f"row_select must be ({V}, {rows}), got {tuple(sel.shape)}")
+    if absdiff.numel() < packed or end > params.numel():
+        raise L.AbdError("reinit_weights: row table / buffer sizes do not agree")
+    n = params.numel()
+    out = torch.empty((V, n), dtype=torch.float32, device=params.device)
+    thr = torch.empty(V, dtype=torch.float32, device=params.device)
+    zeroed = torch.empty(V, dtype=torch.int64, device=params.device)
+    ks = (C.c_int64 * max(V, 1))(*[int(v) for v in k])
+    L.check(L.lib().abd_reinit_weights_f32(params.data_ptr(), n, absdiff.data_ptr(), arr, n_seg, sel.data_ptr(), ks, V,
+                                           out.data_ptr(), thr.data_ptr(), zeroed.data_ptr(),
+                                           L.stream_ptr(params.device)), "abd_reinit_weights_f32")
+    return out, thr, zeroed
+
+
+@reinit_weights.register_fake
+def _(params, absdiff, table, row_select, k):
+    V = len(k)
+    return (params.new_empty((V, params.numel())), params.new_empty((V,)),
+            params.new_empty((V,), dtype=torch.int64))

@@ -495,6 +495,84 @@ size_t abd_smallcnn_finetune_reg_workspace_bytes(const abd_cnn* net, int64_t bat
 int abd_smallcnn_finetune_reg_step(abd_cnn* net, const abd_finetune_reg_args* a, void* workspace,
                                    size_t workspace_bytes, abd_stream_t stream);
 
+/* ------------------------------------------------------------------ TSBD: unlearning, weight change, re-init
+ * Replaces tsbd.py:108-138 train_unlearning (one batch: gradient ASCENT on the loss with Adam, the record
+ * layer's per-neuron gradient norm; the same loop at correlation_analysis.py:41-71), tsbd.py:342-363 /
+ * correlation_analysis.py:76-99 (neuron weight change: |p_unlearned - p_original| per weight and summed
+ * per neuron) and tsbd.py:49-63 zero_reinit_weight for all ratios of the sweep at :371-380.
+ *
+ * Row table: HOST memory, n_seg (1 .. ABD_MAX_SEGMENTS) segments of `rows` rows of `row_len` floats
+ * starting at element `offset` of a flat fp32 buffer, ascending and not overlapping; rows >= 1 and
+ * row_len >= 1, else ABD_E_INVALID.  For smallcnn the conv table is 64 x 4, 64 x 256, 32 x 256 at the
+ * offsets of conv<i>.weight, the bn table 64, 64, 32 rows of length 1 at bn<i>.weight.  The table's rows
+ * are numbered in segment order and its values are "packed" in that order (no gaps between segments).
+ * The table is read before the call returns and reaches the device as kernel arguments.  Buffers need
+ * only their natural 4-byte alignment.  No floating-point atomics; every reduction has a fixed order. */
+typedef struct abd_row_segment {
+  int64_t offset, rows, row_len;
+} abd_row_segment;
+
+/* absdiff = |a - b| (|a| when b == NULL) over the table's rows: one fp32 subtraction and a sign clear,
+ * bit-equal to torch's (a - b).abs().  absdiff_out (optional, device) receives the packed rows;
+ * row_sums (device float[total rows]) the sum of each row, accumulated in double in a fixed order and
+ * rounded to fp32 once. */
+int abd_row_abs_sums_f32(const float* a, const float* b, const abd_row_segment* table, int n_seg,
+                         float* absdiff_out, float* row_sums, abd_stream_t stream);
+
+/* One batch of train_unlearning on the device:
+ *   1. abd_smallcnn_train_step with do_update = 0 at params: the running statistics and
+ *      num_batches_tracked advance once, metrics (optional) accumulate the POSITIVE loss and the hits
+ *   2. grads <- -grads (the .grad that (-loss).backward() leaves) and torch.optim.Adam on it, with
+ *      exactly abd_adam_f32's arithmetic
+ *   3. record_abs_sums[r] = sum |grads[record_offset + r * record_row_len ...]| for the record layer's
+ *      record_rows rows (tsbd.py:126-128); record_rows == 0 records nothing
+ * The net's GEMM precision applies.  batch >= 1, adam_step >= 1 (1-based, after increment).
+ * workspace: abd_smallcnn_unlearn_workspace_bytes(net, batch). */
+typedef struct abd_unlearn_args {
+  const float* x;               /* (B,1,H0,W0)                                        */
+  const int64_t* labels;        /* (B)                                                */
+  int64_t batch;
+  float* params;                /* flat, updated in place                             */
+  float* grads;                 /* flat (written): the gradient of -loss              */
+  float* exp_avg;               /* flat Adam m                                        */
+  float* exp_avg_sq;            /* flat Adam v                                        */
+  float* running;               /* 6 BN buffers packed like abd_train_args.running    */
+  int64_t* num_batches_tracked; /* optional int64[3], += 1                            */
+  int64_t adam_step;
+  float lr, beta1, beta2, eps;
+  uint64_t seed, counter;
+  int64_t row_offset;
+  const uint8_t* mask1_in;      /* optional dropout keep masks (B,flat),(B,128)       */
+  const uint8_t* mask2_in;      /*   NULL -> generated from (seed, counter)           */
+  uint8_t* mask1_out;           /* optional: masks used                               */
+  uint8_t* mask2_out;
+  float* logprobs_out;          /* optional (B,K)                                     */
+  int64_t* metrics;             /* optional ABD_METRICS_WORDS accumulators (device)   */
+  int64_t record_offset, record_rows, record_row_len;
+  float* record_abs_sums;       /* device float[record_rows]                          */
+} abd_unlearn_args;
+size_t abd_smallcnn_unlearn_workspace_bytes(const abd_cnn* net, int64_t batch);
+int abd_smallcnn_unlearn_step(abd_cnn* net, const abd_unlearn_args* a, void* workspace,
+                              size_t workspace_bytes, abd_stream_t stream);
+
+/* The re-initialised parameter sets of n_variants (1 .. ABD_MAX_REINIT_VARIANTS) ratios in one call.
+ *   absdiff     the packed rows abd_row_abs_sums_f32 wrote (device); NaN is the caller's error
+ *   row_select  HOST bytes (n_variants, total rows), nonzero = the neuron is among the variant's top_num
+ *   k           HOST int64[n_variants]: int(m * wratio), m = the number of weights in the selected rows
+ * thr[v] (device float) = the k[v]-th largest absdiff of variant v's selected rows (radix select on the
+ * bit patterns), out[v][i] (device, (n_variants, n_params)) = 0 where i lies in a selected row and its
+ * absdiff >= thr[v] -- ties at the threshold zero more than k weights, as the reference's ``>=`` does
+ * -- else params[i]; parameters outside the table's rows are copied.  zeroed[v] (device int64) = the
+ * number of weights set to zero.  Each out + v * n_params is a params pointer for abd_smallcnn_eval.
+ * ABD_E_INVALID when k[v] < 1 or k[v] > m (the reference's min([]) ValueError), when a variant selects
+ * no row, or when the table has more than ABD_MAX_REINIT_ROWS rows or reaches past n_params. */
+#define ABD_MAX_REINIT_VARIANTS 16
+#define ABD_MAX_REINIT_ROWS 1024
+int abd_reinit_weights_f32(const float* params, int64_t n_params, const float* absdiff,
+                           const abd_row_segment* table, int n_seg, const uint8_t* row_select,
+                           const int64_t* k, int n_variants, float* out, float* thr, int64_t* zeroed,
+                           abd_stream_t stream);
+
 /* ------------------------------------------------------------------ profiling
  * Per-phase HIP-event brackets around libabd launches (bench.py roofline).  Bit i of
  * phase_mask enables phase i (see csrc/prof.h: 0 stft_mel, 1 db_dct, 6 conv2 fwd,
