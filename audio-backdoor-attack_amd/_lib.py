@@ -34,6 +34,8 @@ EXPORTS = (
     "abd_smallcnn_finetune_reg_workspace_bytes", "abd_smallcnn_finetune_reg_step",
     "abd_row_abs_sums_f32", "abd_smallcnn_unlearn_workspace_bytes", "abd_smallcnn_unlearn_step",
     "abd_reinit_weights_f32",
+    "abd_smallcnn_hidden_sums", "abd_smallcnn_fcprune_workspace_bytes", "abd_smallcnn_fcprune_eval",
+    "abd_smallcnn_pruned_finetune_workspace_bytes", "abd_smallcnn_pruned_finetune_step",
     "abd_profile_start", "abd_profile_start_every", "abd_profile_step", "abd_profile_stop",
 )
 
@@ -129,6 +131,23 @@ MAX_REINIT_VARIANTS = 16
 MAX_REINIT_ROWS = 1024
 
 
+class PrunedFinetuneArgs(C.Structure):
+    """abd_pruned_finetune_args: one batch of train_finetuning under prune.custom_from_mask (fp.py:52-76)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("labels", C.c_void_p), ("batch", C.c_int64),
+        ("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("running", C.c_void_p), ("num_batches_tracked", C.c_void_p), ("pruned", C.c_void_p),
+        ("adam_step", C.c_int64), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("seed", C.c_uint64), ("counter", C.c_uint64), ("row_offset", C.c_int64),
+        ("mask1_in", C.c_void_p), ("mask2_in", C.c_void_p), ("mask1_out", C.c_void_p), ("mask2_out", C.c_void_p),
+        ("logprobs_out", C.c_void_p), ("metrics", C.c_void_p),
+    ]
+
+
+FCPRUNE_UNITS = 128            # fc2's inputs: the units fp.py ranks and prunes
+FCPRUNE_PASS_VARIANTS = 128    # variants whose masks one launch carries as kernel arguments
+
+
 # int (*bn_sync)(void* ctx, int point, int64_t offset, int64_t n)  (abd_train_args.bn_sync)
 BN_SYNC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64)
 BN_SYNC_STRIDE = 136
@@ -206,6 +225,11 @@ def _declare(lib):
         "abd_smallcnn_unlearn_step": (i32, [vp, C.POINTER(UnlearnArgs), vp, sz, vp]),
         "abd_reinit_weights_f32": (i32, [vp, i64, vp, C.POINTER(RowSegment), i32, vp, C.POINTER(i64), i32, vp, vp, vp,
                                          vp]),
+        "abd_smallcnn_hidden_sums": (i32, [vp, vp, i64, vp, vp, vp, vp, sz, vp]),
+        "abd_smallcnn_fcprune_workspace_bytes": (sz, [vp, i64, i32]),
+        "abd_smallcnn_fcprune_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
+        "abd_smallcnn_pruned_finetune_workspace_bytes": (sz, [vp, i64]),
+        "abd_smallcnn_pruned_finetune_step": (i32, [vp, C.POINTER(PrunedFinetuneArgs), vp, sz, vp]),
         "abd_profile_start": (i32, [C.c_ulonglong, i32]),
         "abd_profile_start_every": (i32, [C.c_ulonglong, i32, i32]),
         "abd_profile_step": (i32, []),

@@ -9,6 +9,9 @@
     tsbd.py:108-138           train_unlearning                         -> unlearn_epoch
     tsbd.py:342-367           NWC scores, ucn.txt, ranking             -> neuron_weight_change, ucn_text, rank_neurons
     tsbd.py:49-63,371-380     zero_reinit_weight and its ratio sweep   -> reinit_models, reinit_sweep
+    fp.py:131-148             hooked activation mean, argsort          -> hidden_activation, rank_units
+    fp.py:164-195             prune sweep and its stop rule            -> prune_masks, fc_prune_sweep, prune_stop
+    fp.py:52-76,199-210       masked fine-tuning, the whole mitigation -> pruned_finetune_epoch, fine_prune
 
 The reference deep-copies the model per neuron, zeroes ``state_dict[layer][idx]`` and runs a whole
 DataLoader pass: 160 evaluations per set.  Here every batch is evaluated once for all variants
@@ -16,6 +19,8 @@ DataLoader pass: 160 evaluations per set.  Here every batch is evaluated once fo
 in HBM.  There is no CPU path: CPU tensors raise AbdError.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -516,17 +521,235 @@ def reinit_sweep(model, clean_x, clean_y, bd_x, bd_y, bd_indicator, ranked, absd
     K = int(model.state_dict()["fc2.weight"].shape[0])
     prec = getattr(model, "gemm_precision", "f32split")
     clean_y, bd_y, bd_indicator = clean_y.to(torch.int64), bd_y.to(torch.int64), bd_indicator.to(torch.int64)
-    results = []
-    for v in range(len(ratios)):
-        words = []
-        for xs, ys, ind in ((clean_x, clean_y, None), (bd_x, bd_y, bd_indicator)):
-            metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
-            bounds = batch_bounds(int(xs.shape[0]), int(batch_size))
-            for s, e in bounds:
-                torch.ops.abd.smallcnn_eval_metrics(xs[s:e], params[v], running, K, prec, ys[s:e],
-                                                    ind[s:e] if ind is not None else None, metrics)
-            words.append((metrics, len(bounds)))
-        (cl, ct, cc, _, _, _), nc = T.read_metrics(words[0][0]), words[0][1]
-        (bl, _, _, pt, ah, _), nb = T.read_metrics(words[1][0]), words[1][1]
-        results.append((100 * cc / ct, 100 * ah / pt, cl / nc, bl / nb))
-    return results
+    return [_test_numbers(params[v], running, K, prec, clean_x, clean_y, bd_x, bd_y, bd_indicator, batch_size)
+            for v in range(len(ratios))]
+
+
+# ------------------------------------------------------------------ Fine-Pruning (fp.py:131-210)
+# The reference hooks the input of the model's LAST child and prunes the first Linear of that child.  Its
+# smallcnn's last child is the nn.Softmax() that forward never calls: the hook never fires and mitigation()
+# stops with a NameError.  With that unused child deleted from the loaded module the last child is fc2: the
+# pruned layer is fc2 and the ranked units are its 128 inputs, relu(fc1(...)) in eval mode.  That is what
+# these functions reproduce.
+FP_UNITS = L.FCPRUNE_UNITS
+
+
+def _x_batches(x, batch_size, order):
+    N = int(x.shape[0])
+    o = epoch_order(N, order)
+    bounds = batch_bounds(N, int(batch_size))
+    if o is None:
+        return [x[s:e] for s, e in bounds]
+    idx = torch.from_numpy(o).to(x.device)
+    return [x.index_select(0, idx[s:e]) for s, e in bounds]
+
+
+def _check_eval_input(x, what):
+    L.require_device(x, f"{what} input")
+    if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
+        raise ValueError(f"{what} expects (N, 1, T, n_mfcc) float32")
+
+
+def hidden_activation(model, x, batch_size=256, order=None, first_batch_only=True):
+    """The activation vector of fp.py:138-146: the eval-mode input of fc2, summed over rows and divided by the
+    size of the WHOLE set; a (128,) float32 host tensor.  x (N, 1, T, n_mfcc) float32 is device-resident and
+    batched in ``order`` (the shuffled loader's row permutation; default sequential).
+
+    The reference accumulates inside ``if flag == 0:``, so only the FIRST batch contributes while the divisor
+    is len(clean_val_set): that is the default.  first_batch_only=False averages every batch.  The sums are
+    accumulated in double on the device and rounded to float32 once (the reference sums in float32)."""
+    from . import ops  # noqa: F401  (registers torch.ops.abd)
+    _check_eval_input(x, "hidden_activation")
+    if x.shape[0] == 0:
+        raise ValueError("hidden_activation needs at least one row")
+    dev = x.device
+    params, running = _flat_state(model, dev)
+    K = int(model.state_dict()["fc2.weight"].shape[0])
+    prec = getattr(model, "gemm_precision", "f32split")
+    sums = torch.zeros(FP_UNITS, dtype=torch.float64, device=dev)
+    batches = _x_batches(x, batch_size, order)
+    for xb in batches[:1] if first_batch_only else batches:
+        torch.ops.abd.smallcnn_hidden_sums(xb.contiguous(), params, running, sums, K, prec)
+    return (sums / float(x.shape[0])).to(torch.float32).cpu()
+
+
+def rank_units(activation):
+    """seq_sort of fp.py:148: the units in ascending order of their mean activation, a host int64 array.
+    The sort is stable (numpy ``kind='stable'``).  Dead ReLU units tie at exactly 0; torch.argsort on the CPU
+    is not stable, so the reference's own order among tied units is reproduced only where it agrees with the
+    stable one (ascending unit index)."""
+    a = torch.as_tensor(activation).detach().cpu().numpy()
+    if a.ndim != 1:
+        raise ValueError("activation must be one value per unit")
+    return np.argsort(a, kind="stable").astype(np.int64)
+
+
+def prune_masks(seq_sort, once_prune_ratio=0.01):
+    """The steps of fp.py:164-171: (num_pruned list, masks (V, n) uint8 host tensor, nonzero = pruned) for
+    num_pruned = 0, s, 2s, ... < n with s = ceil(n * once_prune_ratio).  Step num_pruned > 0 prunes
+    ``seq_sort[0 : num_pruned - 1]``: one unit fewer than its name says, as the reference's slice does."""
+    import math
+    seq = np.asarray(seq_sort, dtype=np.int64)
+    n = len(seq)
+    nums = list(range(0, n, math.ceil(n * once_prune_ratio)))
+    masks = np.zeros((len(nums), n), np.uint8)
+    for v, num in enumerate(nums):
+        if num:
+            masks[v, seq[0:num - 1]] = 1
+    return nums, torch.from_numpy(masks)
+
+
+def fc_prune_sweep(model, x, y, masks, batch_size=256):
+    """temp_test (fp.py:36-50) of every pruned variant at once: variant v is the eval model with the columns
+    masks[v] of fc2.weight removed.  x, y device-resident, batched in the given order; masks (V, 128) uint8.
+    Returns (loss (V), acc (V)) float64 host tensors through combine().  One eval forward per batch for all
+    variants (torch.ops.abd.smallcnn_fcprune_eval); the model is read, never modified or copied."""
+    from . import ops  # noqa: F401  (registers torch.ops.abd)
+    _check_eval_input(x, "fc_prune_sweep")
+    L.require_device(y, "fc_prune_sweep labels")
+    masks = torch.as_tensor(masks).detach().to("cpu", torch.uint8).contiguous()
+    V, N = int(masks.shape[0]), int(x.shape[0])
+    dev = x.device
+    params, running = _flat_state(model, dev)
+    K = int(model.state_dict()["fc2.weight"].shape[0])
+    prec = getattr(model, "gemm_precision", "f32split")
+    y = y.to(torch.int64)
+    bounds = batch_bounds(N, int(batch_size))
+    loss_sums = torch.zeros((max(len(bounds), 1), V), dtype=torch.float64, device=dev)
+    correct = torch.zeros(V, dtype=torch.int64, device=dev)
+    for i, (s, e) in enumerate(bounds):
+        torch.ops.abd.smallcnn_fcprune_eval(x[s:e], params, running, y[s:e], masks, loss_sums[i], correct, K, prec)
+    return combine(loss_sums.cpu(), [e - s for s, e in bounds] or [1], correct.cpu(), max(N, 1))
+
+
+def prune_stop(num_pruned, accs, acc_ratio=0.1):
+    """The stop rule of fp.py:187-195 over the sweep's clean accuracies: (steps, last_index, stop_index).
+    steps: how many steps the reference's loop runs (the one that broke included); last_index: num_pruned of
+    the last step whose accuracy stayed within acc_ratio of the unpruned one; stop_index: num_pruned of the
+    step at which the loop ended -- the step that broke, or the last one.  The reference's ``last_net`` aliases
+    ``net_pruned``, so the model it fine-tunes carries the mask of stop_index, not of last_index.  An unpruned
+    accuracy of 0 divides by zero, as in the reference."""
+    last_index = stop_index = 0
+    steps = 0
+    for num, acc in zip(num_pruned, accs):
+        steps += 1
+        stop_index = num
+        if num == 0:
+            ori = acc
+            last_index = 0
+        if abs(acc - ori) / ori < acc_ratio:
+            last_index = num
+        else:
+            break
+    return steps, last_index, stop_index
+
+
+def pruned_finetune_epoch(model, x, y, optimizer, unit_mask, batch_size=256, order=None, masks=None):
+    """One epoch of train_finetuning (fp.py:52-76) with prune.custom_from_mask(fc2, 'weight') active: the
+    columns unit_mask (128 values, nonzero = pruned) of fc2.weight are zeroed once, then every batch is one
+    torch.ops.abd.smallcnn_pruned_finetune_step (no-update train step, the pruned columns' gradient zeroed,
+    torch.optim.Adam).  The pruned columns stay exactly zero: fc2.weight is the effective weight.  masks:
+    optional dropout keep-masks per batch [(mask1 (B, flat), mask2 (B, 128))] uint8 device tensors (default:
+    the model's dropout source).  Returns (loss, acc): the sum of the batch-mean losses over the number of
+    batches and correct predictions over samples."""
+    from . import ops, training as T  # noqa: F401  (registers torch.ops.abd)
+    from .models import dropout_seed
+    _check_finetune_inputs(model, x, y, "pruned_finetune_epoch")
+    unit = torch.as_tensor(unit_mask).detach().reshape(-1).to("cpu").ne(0)
+    if unit.numel() != FP_UNITS:
+        raise ValueError(f"unit_mask must hold {FP_UNITS} values")
+    model.train()
+    dev = x.device
+    eng = model.engine(x)
+    adam = _adam_binding(model, optimizer, "pruned_finetune_epoch")
+    pruned = unit.to(torch.uint8).to(dev)
+    with torch.no_grad():
+        model.fc2.weight[:, unit.to(dev)] = 0.0
+    batches = _epoch_batches(x, y, batch_size, order)
+    if masks is not None and len(masks) != len(batches):
+        raise ValueError("masks needs one (mask1, mask2) pair per batch")
+    metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
+    for i, (xb, yb) in enumerate(batches):
+        hm = masks[i] if masks is not None else model.step_masks(int(xb.shape[0]), dev)
+        adam.step += 1
+        torch.ops.abd.smallcnn_pruned_finetune_step(
+            xb.contiguous(), yb.contiguous(), eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, eng.running, eng.nbt,
+            metrics, pruned, None, None, eng.K, adam.step, adam.lr, adam.betas[0], adam.betas[1], adam.eps,
+            dropout_seed(dev, model), model._step, hm[0] if hm is not None else None,
+            hm[1] if hm is not None else None, model.gemm_precision)
+        model._step += 1
+    adam.sync_torch_state()
+    T.expose_grads(model)
+    loss_sum, total, hit, _, _, _ = T.read_metrics(metrics)
+    return loss_sum / len(batches), hit / total
+
+
+def _test_numbers(params, running, K, prec, clean_x, clean_y, bd_x, bd_y, bd_indicator, batch_size):
+    """training.test's (test_clean_acc, test_asr, clean_test_loss, bd_test_loss) of one flat parameter set on
+    device-resident sets (percentages; the losses are means over the batches of the batch-mean loss)."""
+    from . import training as T
+    dev = clean_x.device
+    words = []
+    for xs, ys, ind in ((clean_x, clean_y, None), (bd_x, bd_y, bd_indicator)):
+        metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
+        bounds = batch_bounds(int(xs.shape[0]), int(batch_size))
+        for s, e in bounds:
+            torch.ops.abd.smallcnn_eval_metrics(xs[s:e], params, running, K, prec, ys[s:e],
+                                                ind[s:e] if ind is not None else None, metrics)
+        words.append((metrics, len(bounds)))
+    (cl, ct, cc, _, _, _), nc = T.read_metrics(words[0][0]), words[0][1]
+    (bl, _, _, pt, ah, _), nb = T.read_metrics(words[1][0]), words[1][1]
+    return 100 * cc / ct, 100 * ah / pt, cl / nc, bl / nb
+
+
+class FinePruneResult(NamedTuple):
+    pruning_rows: list        # pruning_data.csv: [num_pruned, pruning_ratio, test_acc, test_asr] per step run
+    ft_row: tuple             # ft_data.csv: (test_clean_acc, test_asr, clean_test_loss, bd_test_loss)
+    unit_mask: torch.Tensor   # (128,) uint8 host tensor, nonzero = pruned: the mask of stop_index
+    model: torch.nn.Module    # the fine-tuned smallcnn; fc2.weight is the effective (masked) weight
+    weight_orig: torch.Tensor  # fc2.weight as prune's weight_orig holds it: pruned columns keep their old values
+    last_index: int
+    stop_index: int
+    activation: torch.Tensor
+    seq_sort: np.ndarray
+    ft_loss: float
+    ft_acc: float
+
+
+def fine_prune(model, val_x, val_y, clean_x, clean_y, bd_x, bd_y, bd_indicator, *, once_prune_ratio=0.01,
+               acc_ratio=0.1, lr_ft=0.01, batch_size=256, val_order=None, ft_order=None, ft_masks=None):
+    """fp.py's mitigation() after its data loading, on device-resident sets: the activation of the first
+    validation batch (hidden_activation), the ranking, the prune sweep over the clean and the backdoor test
+    set (all steps at once, one eval forward per batch), the stop rule on the host (prune_stop), one
+    torch.optim.Adam(lr_ft) fine-tuning epoch over the validation set with the mask of the step at which the
+    loop ENDED (stop_index, see prune_stop), and training.test's four numbers of the result.  val_order /
+    ft_order: the row permutations of the two shuffled passes over the validation loader; ft_masks: see
+    pruned_finetune_epoch.  The given model is read, never modified; the result carries one fine-tuned copy."""
+    import copy
+    from . import ops  # noqa: F401  (registers torch.ops.abd)
+    for t, what in ((val_x, "validation input"), (val_y, "validation labels"), (clean_x, "clean input"),
+                    (clean_y, "clean labels"), (bd_x, "backdoor input"), (bd_y, "backdoor labels"),
+                    (bd_indicator, "backdoor indicator")):
+        L.require_device(t, f"fine_prune {what}")
+    activation = hidden_activation(model, val_x, batch_size, val_order, first_batch_only=True)
+    seq_sort = rank_units(activation)
+    nums, masks = prune_masks(seq_sort, once_prune_ratio)
+    clean_y, bd_y, bd_indicator = clean_y.to(torch.int64), bd_y.to(torch.int64), bd_indicator.to(torch.int64)
+    _, acc = fc_prune_sweep(model, clean_x, clean_y, masks, batch_size)
+    _, asr = fc_prune_sweep(model, bd_x, bd_y, masks, batch_size)
+    acc, asr = acc.tolist(), asr.tolist()
+    steps, last_index, stop_index = prune_stop(nums, acc, acc_ratio)
+    rows = [[nums[i], nums[i] / len(seq_sort), acc[i], asr[i]] for i in range(steps)]
+    unit_mask = masks[steps - 1].clone()
+    tuned = copy.deepcopy(model)
+    orig = tuned.fc2.weight.detach().clone()
+    optimizer = torch.optim.Adam(tuned.parameters(), lr=lr_ft)
+    ft_loss, ft_acc = pruned_finetune_epoch(tuned, val_x, val_y, optimizer, unit_mask, batch_size, ft_order, ft_masks)
+    eng = tuned._engine
+    ft_row = _test_numbers(eng.params, eng.running, eng.K, tuned.gemm_precision, clean_x, clean_y, bd_x, bd_y,
+                           bd_indicator, batch_size)
+    weight_orig = tuned.fc2.weight.detach().clone()
+    keep = unit_mask.ne(0).to(weight_orig.device)
+    weight_orig[:, keep] = orig.to(weight_orig.device)[:, keep]
+    return FinePruneResult(rows, ft_row, unit_mask, tuned, weight_orig, last_index, stop_index, activation, seq_sort,
+                           ft_loss, ft_acc)

@@ -14,6 +14,9 @@
     torch.ops.abd.segment_norms / perturb  per-tensor ``grad.norm()`` and ``param += r * grad / norm`` (ft_reg.py:99-101)
     torch.ops.abd.smallcnn_finetune_reg_step  ft_reg.py:83-123: one batch of train_finetuning_reg -- two gradient
                                        passes, the displaced parameters, SGD, the loss / accuracy forward
+    torch.ops.abd.row_abs_sums / smallcnn_unlearn_step / reinit_weights  tsbd.py's unlearning, scores, re-init sweep
+    torch.ops.abd.smallcnn_hidden_sums / smallcnn_fcprune_eval / smallcnn_pruned_finetune_step  fp.py: the mean
+                                       activation of fc2's input, the prune sweep, the masked Adam fine-tuning step
 
 Each op enqueues its HIP kernels on the current torch stream through the C ABI
 (include/abd.h) and has a fake (meta) implementation, so the ops trace under FakeTensor /
@@ -522,3 +525,123 @@ def _(params, absdiff, table, row_select, k):
     V = len(k)
     return (params.new_empty((V, params.numel())), params.new_empty((V,)),
             params.new_empty((V,), dtype=torch.int64))
+
+
+# --------------------------------------------------------------------------- Fine-Pruning (fp.py)
+@torch.library.custom_op("abd::smallcnn_hidden_sums", mutates_args=("sums",))
+def smallcnn_hidden_sums(x: Tensor, params: Tensor, running: Tensor, sums: Tensor, num_classes: int,
+                         precision: str = "f32split") -> None:
+    """One eval forward of the batch, then sums[u] (float64[128]) += the column sum of fc2's input,
+    relu(fc1(...)), over the batch rows (fp.py:140-146): double accumulation in a fixed order."""
+    L.require_device(x, "smallcnn input")
+    for t, what in ((params, "params"), (running, "running"), (sums, "sums")):
+        L.require_device(t, what)
+    if sums.dtype != torch.float64 or sums.numel() != L.FCPRUNE_UNITS:
+        raise L.AbdError(f"sums must be float64[{L.FCPRUNE_UNITS}]")
+    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    if B == 0:
+        return None
+    h = _net(H0, W0, num_classes, precision)
+    ws = _ws(L.lib().abd_smallcnn_workspace_bytes(h, B), x.device)
+    L.check(L.lib().abd_smallcnn_hidden_sums(h, x.data_ptr(), B, params.data_ptr(), running.data_ptr(), sums.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
+            "abd_smallcnn_hidden_sums")
+    return None
+
+
+@smallcnn_hidden_sums.register_fake
+def _(x, params, running, sums, num_classes, precision="f32split"):
+    return None
+
+
+@torch.library.custom_op("abd::smallcnn_fcprune_eval", mutates_args=("loss_sum", "correct"))
+def smallcnn_fcprune_eval(x: Tensor, params: Tensor, running: Tensor, labels: Tensor, masks: Tensor, loss_sum: Tensor,
+                          correct: Tensor, num_classes: int, precision: str = "f32split") -> None:
+    """The prune sweep on one batch (abd_smallcnn_fcprune_eval): variant v is the eval model with the columns
+    masks[v] of fc2.weight removed; loss_sum[v] (float64) += the batch's summed CE loss, correct[v] (int64) += its
+    correct predictions.  masks is a (V, 128) uint8 HOST tensor, nonzero = pruned; a device tensor is copied to
+    the host first."""
+    L.require_device(x, "smallcnn input")
+    for t, what in ((params, "params"), (running, "running"), (labels, "labels"), (loss_sum, "loss_sum"),
+                    (correct, "correct")):
+        L.require_device(t, what)
+    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    m = masks.detach().to("cpu", torch.uint8).contiguous()
+    if m.dim() != 2 or m.shape[1] != L.FCPRUNE_UNITS:
+        raise L.AbdError(f"masks must be (V, {L.FCPRUNE_UNITS}), got {tuple(m.shape)}")
+    V = int(m.shape[0])
+    if loss_sum.numel() < V or correct.numel() < V or loss_sum.dtype != torch.float64 or correct.dtype != torch.int64:
+        raise L.AbdError("loss_sum (float64) and correct (int64) need one entry per variant")
+    if labels.dtype != torch.int64 or labels.numel() != B:
+        raise L.AbdError("labels must be int64, one per batch row")
+    if B == 0 or V == 0:
+        return None
+    h = _net(H0, W0, num_classes, precision)
+    ws = _ws(L.lib().abd_smallcnn_fcprune_workspace_bytes(h, B, V), x.device)
+    L.check(L.lib().abd_smallcnn_fcprune_eval(h, x.data_ptr(), B, params.data_ptr(), running.data_ptr(),
+                                              labels.data_ptr(), m.data_ptr(), V, loss_sum.data_ptr(),
+                                              correct.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
+            "abd_smallcnn_fcprune_eval")
+    return None
+
+
+@smallcnn_fcprune_eval.register_fake
+def _(x, params, running, labels, masks, loss_sum, correct, num_classes, precision="f32split"):
+    return None
+
+
+@torch.library.custom_op("abd::smallcnn_pruned_finetune_step",
+                         mutates_args=("params", "grads", "exp_avg", "exp_avg_sq", "running", "num_batches_tracked",
+                                       "metrics", "mask1_out", "mask2_out"))
+def smallcnn_pruned_finetune_step(x: Tensor, labels: Tensor, params: Tensor, grads: Tensor, exp_avg: Tensor,
+                                  exp_avg_sq: Tensor, running: Tensor, num_batches_tracked: Tensor, metrics: Tensor,
+                                  pruned: Tensor, mask1_out: Optional[Tensor], mask2_out: Optional[Tensor],
+                                  num_classes: int, adam_step: int, lr: float, beta1: float, beta2: float, eps: float,
+                                  seed: int, counter: int, mask1_in: Optional[Tensor] = None,
+                                  mask2_in: Optional[Tensor] = None, precision: str = "f32split",
+                                  row_offset: int = 0) -> Tensor:
+    """One batch of train_finetuning (fp.py:52-76) with prune.custom_from_mask active on fc2.weight; returns the
+    batch's log-probs (B, K).  A no-update train step at params (which hold the effective weight: the caller
+    zeroed the pruned columns once), the gradient of fc2.weight[:, j] zeroed for every unit j of pruned (a device
+    uint8[128]) and written back, then torch.optim.Adam (step index adam_step >= 1) on it."""
+    L.require_device(x, "smallcnn input")
+    for t, what in ((labels, "labels"), (params, "params"), (grads, "grads"), (exp_avg, "exp_avg"),
+                    (exp_avg_sq, "exp_avg_sq"), (running, "running"), (num_batches_tracked, "num_batches_tracked"),
+                    (metrics, "metrics"), (pruned, "pruned")):
+        L.require_device(t, what)
+    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    h = _net(H0, W0, num_classes, precision)
+    flat = L.lib().abd_smallcnn_flat_features(h)
+    if labels.dtype != torch.int64 or labels.numel() != B:
+        raise L.AbdError("labels must be int64, one per batch row")
+    if pruned.dtype != torch.uint8 or pruned.numel() != L.FCPRUNE_UNITS:
+        raise L.AbdError(f"pruned must be uint8[{L.FCPRUNE_UNITS}]")
+    if (mask1_in is None) != (mask2_in is None) or (mask1_out is None) != (mask2_out is None):
+        raise L.AbdError("dropout masks come in pairs")
+    for m, cols, what in ((mask1_in, flat, "mask1_in"), (mask2_in, 128, "mask2_in"), (mask1_out, flat, "mask1_out"),
+                          (mask2_out, 128, "mask2_out")):
+        if m is not None:
+            L.require_device(m, what)
+            if m.dtype != torch.uint8 or tuple(m.shape) != (B, cols):
+                raise L.AbdError(f"{what} must be uint8 ({B}, {cols}), got {tuple(m.shape)}")
+    a = L.PrunedFinetuneArgs()
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
+    a.x, a.labels, a.batch = x.data_ptr(), labels.data_ptr(), B
+    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
+    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    a.num_batches_tracked, a.pruned = num_batches_tracked.data_ptr(), pruned.data_ptr()
+    a.adam_step, a.lr, a.beta1, a.beta2, a.eps = int(adam_step), float(lr), float(beta1), float(beta2), float(eps)
+    a.seed, a.counter, a.row_offset = int(seed), int(counter), int(row_offset)
+    a.mask1_in, a.mask2_in, a.mask1_out, a.mask2_out = _ptr(mask1_in), _ptr(mask2_in), _ptr(mask1_out), _ptr(mask2_out)
+    a.logprobs_out, a.metrics = out.data_ptr(), metrics.data_ptr()
+    ws = _ws(L.lib().abd_smallcnn_pruned_finetune_workspace_bytes(h, B), x.device)
+    L.check(L.lib().abd_smallcnn_pruned_finetune_step(h, C.byref(a), ws.data_ptr(), ws.numel(),
+                                                      L.stream_ptr(x.device)), "abd_smallcnn_pruned_finetune_step")
+    return out
+
+
+@smallcnn_pruned_finetune_step.register_fake
+def _(x, labels, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics, pruned, mask1_out,
+      mask2_out, num_classes, adam_step, lr, beta1, beta2, eps, seed, counter, mask1_in=None, mask2_in=None,
+      precision="f32split", row_offset=0):
+    return x.new_empty((x.shape[0], num_classes))

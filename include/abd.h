@@ -573,6 +573,79 @@ int abd_reinit_weights_f32(const float* params, int64_t n_params, const float* a
                            const int64_t* k, int n_variants, float* out, float* thr, int64_t* zeroed,
                            abd_stream_t stream);
 
+/* ------------------------------------------------------------------ Fine-Pruning: ranking, prune sweep, masked tuning
+ * Replaces fp.py:131-147 (the mean input activation of the model's last child over clean batches),
+ * fp.py:164-195 (the prune sweep: temp_test of the model with the lowest units masked out of the first
+ * Linear of that child, for every step) and fp.py:52-76 train_finetuning under prune.custom_from_mask.
+ * The reference's last child of smallcnn is the unused nn.Softmax(); with it deleted the last child is
+ * fc2, the pruned layer is fc2 and its input is relu(fc1(...)) in eval mode, ABD_FCPRUNE_UNITS units.
+ * The network passes are abd_smallcnn_eval / abd_smallcnn_train_step (do_update = 0) themselves: every
+ * GEMM precision they support applies unchanged (ABD_PREC_BF16 included; fc2 and the loss are fp32 in
+ * all of them).  No floating-point atomics; every reduction has a fixed order. */
+#define ABD_FCPRUNE_UNITS 128
+#define ABD_FCPRUNE_PASS_VARIANTS 128
+
+/* One eval forward of the batch, then sums[u] += sum over the rows of fc2's input unit u, accumulated
+ * in double in a fixed order.  sums: device double[ABD_FCPRUNE_UNITS], accumulates over calls (zero it
+ * before the first).  batch == 0 launches nothing.  workspace: abd_smallcnn_workspace_bytes(net, batch). */
+int abd_smallcnn_hidden_sums(abd_cnn* net, const float* x, int64_t batch, const float* params,
+                             const float* running, double* sums, void* workspace,
+                             size_t workspace_bytes, abd_stream_t stream);
+
+/* The prune sweep on one batch: ONE eval forward, then per variant v and row fc2 with the pruned units'
+ * columns removed, log_softmax, nn.CrossEntropyLoss on the log-probs (temp_test, fp.py:36-50) and the
+ * arg-max (first index on ties).
+ *   masks   HOST memory, (n_variants, ABD_FCPRUNE_UNITS) bytes, nonzero = pruned.  Any mask: empty (the
+ *           baseline), all units (the logits equal the bias), nested or not.  Read before the call
+ *           returns; it reaches the device as kernel arguments, ABD_FCPRUNE_PASS_VARIANTS variants per
+ *           pass (any n_variants, the tail pass included), so the launch sequence stays capture-safe.
+ *   loss_sum[v] += sum over the batch rows of the CE loss (double), correct[v] += rows whose arg-max is
+ *           the label (int64): device buffers of n_variants entries that accumulate over calls, the
+ *           accumulators of abd_smallcnn_ablate_eval.
+ * batch == 0 or n_variants == 0 launches nothing.  labels must lie in [0, num_classes).
+ * workspace: abd_smallcnn_fcprune_workspace_bytes(net, batch, n_variants). */
+size_t abd_smallcnn_fcprune_workspace_bytes(const abd_cnn* net, int64_t batch, int n_variants);
+int abd_smallcnn_fcprune_eval(abd_cnn* net, const float* x, int64_t batch, const float* params,
+                              const float* running, const int64_t* labels, const uint8_t* masks,
+                              int n_variants, double* loss_sum, int64_t* correct, void* workspace,
+                              size_t workspace_bytes, abd_stream_t stream);
+
+/* One batch of train_finetuning (fp.py:52-76) with prune.custom_from_mask active on fc2.weight:
+ *   1. abd_smallcnn_train_step with do_update = 0 at params (whose pruned fc2.weight columns the caller
+ *      zeroed once: params holds the EFFECTIVE weight); running statistics and num_batches_tracked
+ *      advance once, metrics (optional) accumulate the loss and the hits
+ *   2. grads at fc2.weight[:, j] <- 0 for every pruned unit j, written back: the .grad torch leaves on
+ *      weight_orig
+ *   3. torch.optim.Adam on it, with exactly abd_adam_f32's arithmetic
+ * With zero gradient and zero moments the pruned columns stay exactly zero.  pruned: device
+ * uint8[ABD_FCPRUNE_UNITS], nonzero = pruned.  batch >= 1, adam_step >= 1 (1-based, after increment).
+ * workspace: abd_smallcnn_pruned_finetune_workspace_bytes(net, batch). */
+typedef struct abd_pruned_finetune_args {
+  const float* x;               /* (B,1,H0,W0)                                        */
+  const int64_t* labels;        /* (B)                                                */
+  int64_t batch;
+  float* params;                /* flat, updated in place                             */
+  float* grads;                 /* flat (written): the masked gradient                */
+  float* exp_avg;               /* flat Adam m                                        */
+  float* exp_avg_sq;            /* flat Adam v                                        */
+  float* running;               /* 6 BN buffers packed like abd_train_args.running    */
+  int64_t* num_batches_tracked; /* optional int64[3], += 1                            */
+  const uint8_t* pruned;        /* device uint8[ABD_FCPRUNE_UNITS]                    */
+  int64_t adam_step;
+  float lr, beta1, beta2, eps;
+  uint64_t seed, counter;
+  int64_t row_offset;
+  const uint8_t* mask1_in;      /* optional dropout keep masks (B,flat),(B,128)       */
+  const uint8_t* mask2_in;      /*   NULL -> generated from (seed, counter)           */
+  uint8_t* mask1_out;           /* optional: masks used                               */
+  uint8_t* mask2_out;
+  float* logprobs_out;          /* optional (B,K)                                     */
+  int64_t* metrics;             /* optional ABD_METRICS_WORDS accumulators (device)   */
+} abd_pruned_finetune_args;
+size_t abd_smallcnn_pruned_finetune_workspace_bytes(const abd_cnn* net, int64_t batch);
+int abd_smallcnn_pruned_finetune_step(abd_cnn* net, const abd_pruned_finetune_args* a, void* workspace,
+                                      size_t workspace_bytes, abd_stream_t stream);
+
 /* ------------------------------------------------------------------ profiling
  * Per-phase HIP-event brackets around libabd launches (bench.py roofline).  Bit i of
  * phase_mask enables phase i (see csrc/prof.h: 0 stft_mel, 1 db_dct, 6 conv2 fwd,
