@@ -33,7 +33,7 @@ EXPORTS = (
     "abd_segment_norms_workspace_bytes", "abd_segment_norms_f32", "abd_perturb_f32", "abd_sgd_f32",
     "abd_smallcnn_finetune_reg_workspace_bytes", "abd_smallcnn_finetune_reg_step",
     "abd_row_abs_sums_f32", "abd_smallcnn_unlearn_workspace_bytes", "abd_smallcnn_unlearn_step",
-    "abd_reinit_weights_f32",
+    "abd_reinit_weights_f32", "abd_smallcnn_unlearn_run", "abd_nwc_pair_f32",
     "abd_smallcnn_hidden_sums", "abd_smallcnn_fcprune_workspace_bytes", "abd_smallcnn_fcprune_eval",
     "abd_smallcnn_pruned_finetune_workspace_bytes", "abd_smallcnn_pruned_finetune_step",
     "abd_profile_start", "abd_profile_start_every", "abd_profile_step", "abd_profile_stop",
@@ -129,6 +129,7 @@ class UnlearnArgs(C.Structure):
 
 MAX_REINIT_VARIANTS = 16
 MAX_REINIT_ROWS = 1024
+NWC_STATS_WORDS = 9   # abd_nwc_pair_f32's stats: n, mean_x, mean_y, sxx, syy, sxy, r, slope, intercept
 
 
 class PrunedFinetuneArgs(C.Structure):
@@ -225,6 +226,8 @@ def _declare(lib):
         "abd_smallcnn_unlearn_step": (i32, [vp, C.POINTER(UnlearnArgs), vp, sz, vp]),
         "abd_reinit_weights_f32": (i32, [vp, i64, vp, C.POINTER(RowSegment), i32, vp, C.POINTER(i64), i32, vp, vp, vp,
                                          vp]),
+        "abd_smallcnn_unlearn_run": (i32, [vp, C.POINTER(UnlearnArgs), i64, vp, sz, vp]),
+        "abd_nwc_pair_f32": (i32, [vp, vp, vp, C.POINTER(RowSegment), i32, vp, vp, vp, vp, vp, vp, vp]),
         "abd_smallcnn_hidden_sums": (i32, [vp, vp, i64, vp, vp, vp, vp, sz, vp]),
         "abd_smallcnn_fcprune_workspace_bytes": (sz, [vp, i64, i32]),
         "abd_smallcnn_fcprune_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),

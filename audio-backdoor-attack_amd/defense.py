@@ -9,6 +9,9 @@
     tsbd.py:108-138           train_unlearning                         -> unlearn_epoch
     tsbd.py:342-367           NWC scores, ucn.txt, ranking             -> neuron_weight_change, ucn_text, rank_neurons
     tsbd.py:49-63,371-380     zero_reinit_weight and its ratio sweep   -> reinit_models, reinit_sweep
+    correlation_analysis.py:41-71,141-143   the unlearning loop          -> unlearn_run
+    correlation_analysis.py:128-158  two unlearnings, NWC, Pearson      -> correlation_analysis, correlation_csv,
+                                                                           save_correlation_outputs
     fp.py:131-148             hooked activation mean, argsort          -> hidden_activation, rank_units
     fp.py:164-195             prune sweep and its stop rule            -> prune_masks, fc_prune_sweep, prune_stop
     fp.py:52-76,199-210       masked fine-tuning, the whole mitigation -> pruned_finetune_epoch, fine_prune
@@ -523,6 +526,180 @@ def reinit_sweep(model, clean_x, clean_y, bd_x, bd_y, bd_indicator, ranked, absd
     clean_y, bd_y, bd_indicator = clean_y.to(torch.int64), bd_y.to(torch.int64), bd_indicator.to(torch.int64)
     return [_test_numbers(params[v], running, K, prec, clean_x, clean_y, bd_x, bd_y, bd_indicator, batch_size)
             for v in range(len(ratios))]
+
+
+# ------------------------------------------------------------------ correlation_analysis.py:102-158
+class CorrelationResult(NamedTuple):
+    correlation: float        # df['Clean_unlearn'].corr(df['Poison_unlearn']) (Pearson); NaN for a constant column
+    slope: float              # the least-squares line the reference's sns.lmplot draws: Poison_unlearn over
+    intercept: float          # Clean_unlearn (no plot is produced here)
+    names: list               # 'conv1.weight.0' ...: the rows of both score vectors
+    clean_scores: np.ndarray  # float64 per-neuron sums of the clean-unlearned model: the CSV's Clean_unlearn
+    bd_scores: np.ndarray     # float64, the poison-unlearned model: the CSV's Poison_unlearn
+    ucn_clean: str            # the text of ucn_cleanunlr.txt (the float32 row sums, 4 decimals)
+    ucn_bd: str               # the text of ucn_bdunlr.txt
+    absdiff_clean: torch.Tensor   # packed per-weight changes (device float32): n2w_dict_cleanunlr.pt's values
+    absdiff_bd: torch.Tensor
+    model_clean: torch.nn.Module  # model_cleanunlr
+    model_bd: torch.nn.Module     # model_bdunlr
+    clean_losses: list        # train_unlearning's (loss, acc) of every step, per model
+    clean_accs: list
+    bd_losses: list
+    bd_accs: list
+    clean_unlr_loss: float    # the reference's variables of these names after its loop: it assigns BOTH models'
+    clean_unlr_acc: float     # return values to them, so they end as the poison-unlearned model's last step
+    layer_type: str
+
+
+def unlearn_run(model, x, y, optimizer, n_steps, batch_size=256, order=None, masks=None):
+    """n_steps calls of correlation_analysis.py's train_unlearning (:41-71) in one device call
+    (torch.ops.abd.smallcnn_unlearn_run).  Its loaders are unshuffled and the function returns inside its batch
+    loop, so every call trains on the same rows: the first batch of ``order`` (default sequential).  Returns
+    (losses, accs), one entry per step with the reference's divisors: the batch's mean loss over the NUMBER OF
+    BATCHES of the set, the batch's hits over the SIZE of the set.  No record layer.  Afterwards the Adam
+    state and the parameters' .grad are as unlearn_epoch leaves them; model._step and the optimizer's step
+    count have advanced by n_steps.  masks: an optional (mask1 (n_steps, B, flat), mask2 (n_steps, B, 128))
+    pair of uint8 device tensors; with the 'torch_cpu' dropout source the n_steps pairs are drawn up front,
+    in step order."""
+    from . import ops, training as T  # noqa: F401  (registers torch.ops.abd)
+    from .models import dropout_seed
+    _check_finetune_inputs(model, x, y, "unlearn_run")
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise ValueError(f"unlearn_run needs n_steps >= 1, got {n_steps}")
+    model.train()
+    dev = x.device
+    N = int(x.shape[0])
+    bounds = batch_bounds(N, int(batch_size))
+    s, e = bounds[0]
+    o = epoch_order(N, order)
+    y = y.to(torch.int64)
+    if o is None:
+        xb, yb = x[s:e], y[s:e]
+    else:
+        idx = torch.from_numpy(o[s:e]).to(dev)
+        xb, yb = x.index_select(0, idx), y.index_select(0, idx)
+    xb, yb = xb.contiguous(), yb.contiguous()
+    eng = model.engine(xb)
+    adam = _adam_binding(model, optimizer, "unlearn_run")
+    B = e - s
+    if masks is None and getattr(model, "dropout_source", "device") == "torch_cpu":
+        drawn = [model.step_masks(B, dev) for _ in range(n_steps)]
+        masks = torch.stack([d[0] for d in drawn]), torch.stack([d[1] for d in drawn])
+    m1, m2 = masks if masks is not None else (None, None)
+    metrics = torch.zeros((n_steps, L.METRICS_WORDS), dtype=torch.int64, device=dev)
+    torch.ops.abd.smallcnn_unlearn_run(
+        xb, yb, eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, eng.running, eng.nbt, metrics, None, None, eng.K,
+        n_steps, adam.step + 1, adam.lr, adam.betas[0], adam.betas[1], adam.eps, dropout_seed(dev, model), model._step,
+        m1, m2, model.gemm_precision)
+    adam.step += n_steps
+    model._step += n_steps
+    adam.sync_torch_state()
+    T.expose_grads(model)
+    words = metrics.cpu().numpy()
+    loss_sums = np.ascontiguousarray(words[:, 0]).view(np.float64)
+    return [float(v) / len(bounds) for v in loss_sums], [float(h) / N for h in words[:, 2]]
+
+
+def correlation_stats(clean_scores, bd_scores):
+    """(r, slope, intercept) of two score vectors in float64 numpy with abd_nwc_pair_f32's formulas: means, then
+    centred sums; r = sxy / sqrt(sxx * syy) (NaN for fewer than 2 rows or a constant column), slope = sxy / sxx
+    and intercept = mean_y - slope * mean_x (NaN for a constant x).  Host twin of the device statistics."""
+    x, y = np.asarray(clean_scores, np.float64), np.asarray(bd_scores, np.float64)
+    if x.shape != y.shape or x.ndim != 1 or x.size == 0:
+        raise ValueError("two equally long, non-empty score vectors are needed")
+    mx, my = x.mean(), y.mean()
+    sxx, syy, sxy = ((x - mx) ** 2).sum(), ((y - my) ** 2).sum(), ((x - mx) * (y - my)).sum()
+    r = float("nan") if x.size < 2 or sxx * syy == 0 else float(sxy / np.sqrt(sxx * syy))
+    if sxx == 0:
+        return r, float("nan"), float("nan")
+    slope = float(sxy / sxx)
+    return r, slope, float(my - slope * mx)
+
+
+def correlation_analysis(bd_model, clean_x, clean_y, bd_x, bd_y, *, lr_un=1e-4, unlearn_epochs=1000, batch_size=256,
+                         layer_type="conv", order=None, masks=None):
+    """unlearning_correlation_analysis (correlation_analysis.py:128-158) on device-resident sets: two deep
+    copies of bd_model (read, never modified), torch.optim.Adam(lr_un) for each, unlearn_epochs steps of
+    unlearn_run on the clean rows for one and on the backdoor rows for the other -- both over the SAME
+    ``order``, as the reference applies one shuffle_indices to both sets (default sequential) -- then one
+    torch.ops.abd.nwc_pair call.  masks: optional ((mask1, mask2) of the clean model, (mask1, mask2) of the
+    poisoned one), see unlearn_run; by default each copy draws its own dropout stream, as the reference's two
+    models draw from one advancing generator.  Returns a CorrelationResult.
+
+    Two quirks of the reference are kept.  Its loop assigns the return values of BOTH models' epochs to
+    clean_unlr_loss / clean_unlr_acc: the fields of that name hold the poison-unlearned model's last step (the
+    per-step lists hold everything).  Its CSV and correlation are made from Python ``sum()`` over the
+    float32-valued per-weight lists -- a sequential DOUBLE sum -- not from the float32 ``sum(dim=-1)`` that the
+    ucn text prints: clean_scores / bd_scores are the unrounded double row sums, ucn_* the float32 ones."""
+    import copy
+    from . import ops  # noqa: F401  (registers torch.ops.abd)
+    for t, what in ((clean_x, "clean input"), (clean_y, "clean labels"), (bd_x, "backdoor input"),
+                    (bd_y, "backdoor labels")):
+        L.require_device(t, f"correlation_analysis {what}")
+    if clean_x.shape[0] != bd_x.shape[0]:
+        raise ValueError("the clean and the backdoor set hold the same rows (one shuffle_indices serves both)")
+    names = neuron_names(bd_model, layer_type)
+    if masks is None and getattr(bd_model, "dropout_source", "device") == "torch_cpu":
+        # the reference's CPU stream: clean step i draws before poisoned step i (its loop alternates the models)
+        B = batch_bounds(int(clean_x.shape[0]), int(batch_size))[0][1]
+        drawn = [bd_model.step_masks(B, clean_x.device) for _ in range(2 * int(unlearn_epochs))]
+        masks = tuple((torch.stack([d[0] for d in drawn[k::2]]), torch.stack([d[1] for d in drawn[k::2]]))
+                      for k in (0, 1))
+    per_model = masks if masks is not None else (None, None)
+    runs = []
+    for (xs, ys), mk in zip(((clean_x, clean_y), (bd_x, bd_y)), per_model):
+        m = copy.deepcopy(bd_model)
+        m._dropout_nonce = None            # its own mask stream, drawn when it binds
+        opt = torch.optim.Adam(m.parameters(), lr=lr_un)
+        losses, accs = unlearn_run(m, xs, ys, opt, unlearn_epochs, batch_size, order, mk)
+        runs.append((m, losses, accs))
+    (mc, lc, ac), (mb, lb, ab) = runs
+    dev = clean_x.device
+    orig = _flat_params(bd_model, dev)
+    ad_c, ad_b, s32_c, s32_b, s64, stats = torch.ops.abd.nwc_pair(orig, mc._engine.params, mb._engine.params,
+                                                                  row_table(bd_model, layer_type))
+    s64, stats = s64.cpu().numpy(), stats.cpu().numpy()
+    return CorrelationResult(float(stats[6]), float(stats[7]), float(stats[8]), names, s64[0].copy(), s64[1].copy(),
+                             ucn_text(names, s32_c.cpu().numpy()), ucn_text(names, s32_b.cpu().numpy()), ad_c, ad_b,
+                             mc, mb, lc, ac, lb, ab, lb[-1], ab[-1], layer_type)
+
+
+def correlation_csv(clean_scores, bd_scores):
+    """The text of the reference's clean_poison_unlearn.csv (``df.to_csv(index=False)``, :153-156): the header
+    Clean_unlearn,Poison_unlearn, then one row per neuron with both values as ``repr(float)``, '\n' line ends."""
+    lines = ["Clean_unlearn,Poison_unlearn\n"]
+    for c, b in zip(clean_scores, bd_scores):
+        lines.append(f"{float(c)!r},{float(b)!r}\n")
+    return "".join(lines)
+
+
+CORRELATION_FILES = ("ucn_cleanunlr.txt", "ucn_bdunlr.txt", "n2w_dict_cleanunlr.pt", "n2w_dict_bdunlr.pt",
+                     "unlearned_model_cleanunlr.pt", "unlearned_model_bdunlr.pt", "clean_poison_unlearn.csv")
+
+
+def save_correlation_outputs(result, directory):
+    """The files correlation_analysis.py leaves in its analysis/ folder, under its names (CORRELATION_FILES):
+    the two ucn texts, the two n2w dicts {neuron name: list of per-weight changes} (absdiff_rows), the two
+    unlearned models' state dicts and the CSV.  No scatter plot: the fitted line's coefficients are
+    result.slope / result.intercept.  Returns the paths written."""
+    import os
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for tag, text, absdiff, model in (("cleanunlr", result.ucn_clean, result.absdiff_clean, result.model_clean),
+                                      ("bdunlr", result.ucn_bd, result.absdiff_bd, result.model_bd)):
+        p = os.path.join(directory, f"ucn_{tag}.txt")
+        with open(p, "w", newline="") as f:
+            f.write(text)
+        n2w = os.path.join(directory, f"n2w_dict_{tag}.pt")
+        torch.save(absdiff_rows(model, absdiff, result.layer_type), n2w)
+        sd = os.path.join(directory, f"unlearned_model_{tag}.pt")
+        torch.save(model.state_dict(), sd)
+        paths += [p, n2w, sd]
+    p = os.path.join(directory, "clean_poison_unlearn.csv")
+    with open(p, "w", newline="") as f:
+        f.write(correlation_csv(result.clean_scores, result.bd_scores))
+    return paths + [p]
 
 
 # ------------------------------------------------------------------ Fine-Pruning (fp.py:131-210)

@@ -15,6 +15,8 @@
     torch.ops.abd.smallcnn_finetune_reg_step  ft_reg.py:83-123: one batch of train_finetuning_reg -- two gradient
                                        passes, the displaced parameters, SGD, the loss / accuracy forward
     torch.ops.abd.row_abs_sums / smallcnn_unlearn_step / reinit_weights  tsbd.py's unlearning, scores, re-init sweep
+    torch.ops.abd.smallcnn_unlearn_run / nwc_pair  correlation_analysis.py: the unlearning loop on its one fixed
+                                       batch, both models' weight-change sums and their Pearson correlation
     torch.ops.abd.smallcnn_hidden_sums / smallcnn_fcprune_eval / smallcnn_pruned_finetune_step  fp.py: the mean
                                        activation of fc2's input, the prune sweep, the masked Adam fine-tuning step
 
@@ -525,6 +527,105 @@ def _(params, absdiff, table, row_select, k):
     V = len(k)
     return (params.new_empty((V, params.numel())), params.new_empty((V,)),
             params.new_empty((V,), dtype=torch.int64))
+
+
+# --------------------------------------------------------------------------- correlation_analysis.py
+@torch.library.custom_op("abd::smallcnn_unlearn_run",
+                         mutates_args=("params", "grads", "exp_avg", "exp_avg_sq", "running", "num_batches_tracked",
+                                       "metrics", "mask1_out", "mask2_out"))
+def smallcnn_unlearn_run(x: Tensor, labels: Tensor, params: Tensor, grads: Tensor, exp_avg: Tensor,
+                         exp_avg_sq: Tensor, running: Tensor, num_batches_tracked: Tensor, metrics: Tensor,
+                         mask1_out: Optional[Tensor], mask2_out: Optional[Tensor], num_classes: int, n_steps: int,
+                         adam_step: int, lr: float, beta1: float, beta2: float, eps: float, seed: int, counter: int,
+                         mask1_in: Optional[Tensor] = None, mask2_in: Optional[Tensor] = None,
+                         precision: str = "f32split", row_offset: int = 0) -> Tensor:
+    """n_steps calls of correlation_analysis.py's train_unlearning (:41-71) on one fixed batch in one library call;
+    returns the last step's log-probs (B, K).  Step i is abd::smallcnn_unlearn_step with adam_step + i and
+    counter + i and no record layer, bit for bit.  metrics is int64 (n_steps, 8), zeroed by the caller: row i
+    holds step i's loss and hits.  The masks, when given, are (n_steps, B, flat) and (n_steps, B, 128) uint8."""
+    L.require_device(x, "smallcnn input")
+    for t, what in ((labels, "labels"), (params, "params"), (grads, "grads"), (exp_avg, "exp_avg"),
+                    (exp_avg_sq, "exp_avg_sq"), (running, "running"), (num_batches_tracked, "num_batches_tracked"),
+                    (metrics, "metrics")):
+        L.require_device(t, what)
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise L.AbdError(f"smallcnn_unlearn_run needs n_steps >= 1, got {n_steps}")
+    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    h = _net(H0, W0, num_classes, precision)
+    flat = L.lib().abd_smallcnn_flat_features(h)
+    if labels.dtype != torch.int64 or labels.numel() != B:
+        raise L.AbdError("labels must be int64, one per batch row")
+    if metrics.dtype != torch.int64 or tuple(metrics.shape) != (n_steps, L.METRICS_WORDS):
+        raise L.AbdError(f"metrics must be int64 ({n_steps}, {L.METRICS_WORDS}), got {tuple(metrics.shape)}")
+    if (mask1_in is None) != (mask2_in is None) or (mask1_out is None) != (mask2_out is None):
+        raise L.AbdError("dropout masks come in pairs")
+    for m, cols, what in ((mask1_in, flat, "mask1_in"), (mask2_in, 128, "mask2_in"), (mask1_out, flat, "mask1_out"),
+                          (mask2_out, 128, "mask2_out")):
+        if m is not None:
+            L.require_device(m, what)
+            if m.dtype != torch.uint8 or tuple(m.shape) != (n_steps, B, cols):
+                raise L.AbdError(f"{what} must be uint8 ({n_steps}, {B}, {cols}), got {tuple(m.shape)}")
+    a = L.UnlearnArgs()
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
+    a.x, a.labels, a.batch = x.data_ptr(), labels.data_ptr(), B
+    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
+    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    a.num_batches_tracked = num_batches_tracked.data_ptr()
+    a.adam_step, a.lr, a.beta1, a.beta2, a.eps = int(adam_step), float(lr), float(beta1), float(beta2), float(eps)
+    a.seed, a.counter, a.row_offset = int(seed), int(counter), int(row_offset)
+    a.mask1_in, a.mask2_in, a.mask1_out, a.mask2_out = _ptr(mask1_in), _ptr(mask2_in), _ptr(mask1_out), _ptr(mask2_out)
+    a.logprobs_out, a.metrics = out.data_ptr(), metrics.data_ptr()
+    ws = _ws(L.lib().abd_smallcnn_unlearn_workspace_bytes(h, B), x.device)
+    L.check(L.lib().abd_smallcnn_unlearn_run(h, C.byref(a), n_steps, ws.data_ptr(), ws.numel(),
+                                             L.stream_ptr(x.device)), "abd_smallcnn_unlearn_run")
+    return out
+
+
+@smallcnn_unlearn_run.register_fake
+def _(x, labels, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics, mask1_out, mask2_out,
+      num_classes, n_steps, adam_step, lr, beta1, beta2, eps, seed, counter, mask1_in=None, mask2_in=None,
+      precision="f32split", row_offset=0):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::nwc_pair", mutates_args=())
+def nwc_pair(orig: Tensor, params_a: Tensor, params_b: Tensor, table: list[int],
+             want_absdiff: bool = True) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """correlation_analysis.py:146-157 for two unlearned flat parameter buffers against the original:
+    (absdiff_a, absdiff_b, sums32_a, sums32_b, sums64 (2, rows) float64, stats (9) float64).  absdiff_* and
+    sums32_* are bit-equal to abd::row_abs_sums(params_*, orig, table); sums64 holds the same row sums before
+    their rounding to fp32; stats = [n, mean_x, mean_y, sxx, syy, sxy, r, slope, intercept] of x = sums64[0],
+    y = sums64[1].  At most 1024 rows.  want_absdiff False returns empty absdiff tensors."""
+    for t, what in ((orig, "nwc_pair orig"), (params_a, "nwc_pair params_a"), (params_b, "nwc_pair params_b")):
+        L.require_device(t, what)
+        if t.dtype != torch.float32 or t.numel() != orig.numel():
+            raise L.AbdError("nwc_pair expects three float32 buffers of one size")
+    arr, n_seg, vals = _row_table(table)
+    if min(vals) < 0:
+        raise L.AbdError("row table entries must not be negative")
+    rows, packed, end = _table_extent(vals)
+    if end > orig.numel():
+        raise L.AbdError("row table reaches past the buffer")
+    dev = orig.device
+    absdiff = [torch.empty(packed if want_absdiff else 0, dtype=torch.float32, device=dev) for _ in range(2)]
+    sums32 = [torch.empty(rows, dtype=torch.float32, device=dev) for _ in range(2)]
+    sums64 = torch.empty((2, rows), dtype=torch.float64, device=dev)
+    stats = torch.empty(L.NWC_STATS_WORDS, dtype=torch.float64, device=dev)
+    L.check(L.lib().abd_nwc_pair_f32(orig.data_ptr(), params_a.data_ptr(), params_b.data_ptr(), arr, n_seg,
+                                     absdiff[0].data_ptr() if want_absdiff else None,
+                                     absdiff[1].data_ptr() if want_absdiff else None, sums32[0].data_ptr(),
+                                     sums32[1].data_ptr(), sums64.data_ptr(), stats.data_ptr(), L.stream_ptr(dev)),
+            "abd_nwc_pair_f32")
+    return absdiff[0], absdiff[1], sums32[0], sums32[1], sums64, stats
+
+
+@nwc_pair.register_fake
+def _(orig, params_a, params_b, table, want_absdiff=True):
+    rows, packed, _ = _table_extent([int(v) for v in table])
+    n = packed if want_absdiff else 0
+    return (orig.new_empty((n,)), orig.new_empty((n,)), orig.new_empty((rows,)), orig.new_empty((rows,)),
+            orig.new_empty((2, rows), dtype=torch.float64), orig.new_empty((L.NWC_STATS_WORDS,), dtype=torch.float64))
 
 
 # --------------------------------------------------------------------------- Fine-Pruning (fp.py)

@@ -573,6 +573,46 @@ int abd_reinit_weights_f32(const float* params, int64_t n_params, const float* a
                            const int64_t* k, int n_variants, float* out, float* thr, int64_t* zeroed,
                            abd_stream_t stream);
 
+/* ------------------------------------------------------------------ correlation analysis of two unlearnings
+ * Replaces correlation_analysis.py:141-157: the unlearning loop (every call of train_unlearning there
+ * trains on the FIRST batch of an unshuffled loader, so all --unlearn_epochs steps of a model see one fixed
+ * batch) and the per-neuron weight-change sums of the clean- and the poison-unlearned model with their
+ * Pearson correlation.
+ *
+ * abd_smallcnn_unlearn_run enqueues n_steps (>= 1) unlearning steps on the batch of `a`: step i is exactly
+ * abd_smallcnn_unlearn_step with adam_step + i and counter + i, so the result is bit-equal to n_steps
+ * separate calls in every GEMM precision.  One host call, no synchronisation, nothing allocated.
+ *   mask1_in / mask2_in    optional, n_steps consecutive mask sets: (n_steps, B, flat), (n_steps, B, 128)
+ *   mask1_out / mask2_out  optional, likewise
+ *   metrics                optional int64 (n_steps, ABD_METRICS_WORDS), zeroed by the caller: row i
+ *                          accumulates step i only
+ *   logprobs_out           optional (B, K): the last step's values
+ * The record fields must be unset (record_rows == 0, record_abs_sums == NULL): correlation_analysis.py's
+ * train_unlearning records nothing.  ABD_E_INVALID for n_steps < 1, set record fields and whatever the
+ * step refuses.  workspace: abd_smallcnn_unlearn_workspace_bytes(net, batch). */
+int abd_smallcnn_unlearn_run(abd_cnn* net, const abd_unlearn_args* a, int64_t n_steps, void* workspace,
+                             size_t workspace_bytes, abd_stream_t stream);
+
+/* get_neuron_weight_change (correlation_analysis.py:76-99) of two unlearned parameter sets against one
+ * original, and :149-157 on the result.  Row table as for abd_row_abs_sums_f32, at most
+ * ABD_MAX_REINIT_ROWS rows in all (one block computes the statistics), else ABD_E_INVALID.  Two launches,
+ * no atomics.
+ *   absdiff_a / absdiff_b  optional: the packed |params_a - orig| and |params_b - orig|
+ *   sums32_a / sums32_b    float[rows]: their row sums, bit-equal to abd_row_abs_sums_f32 (the ucn text)
+ *   sums64                 double[2][rows], a first: the same sums before their rounding to fp32 (the
+ *                          reference's CSV holds Python's sequential double sum() of the fp32 values; the
+ *                          order here is the lane groups', within row_len * 2^-53 relative of it)
+ *   stats                  double[ABD_NWC_STATS_WORDS] = {n, mean_x, mean_y, sxx, syy, sxy, r, slope,
+ *                          intercept} with x = sums64[0] (a: the clean-unlearned model), y = sums64[1]:
+ *                          means first, then the centred sums, all in double in a fixed order;
+ *                          r = sxy / sqrt(sxx * syy), NaN when n < 2 or sxx * syy == 0 (pandas' value for
+ *                          a constant column); slope = sxy / sxx and intercept = mean_y - slope * mean_x,
+ *                          the least-squares line of the reference's lmplot, NaN when sxx == 0 */
+#define ABD_NWC_STATS_WORDS 9
+int abd_nwc_pair_f32(const float* orig, const float* params_a, const float* params_b,
+                     const abd_row_segment* table, int n_seg, float* absdiff_a, float* absdiff_b,
+                     float* sums32_a, float* sums32_b, double* sums64, double* stats, abd_stream_t stream);
+
 /* ------------------------------------------------------------------ Fine-Pruning: ranking, prune sweep, masked tuning
  * Replaces fp.py:131-147 (the mean input activation of the model's last child over clean batches),
  * fp.py:164-195 (the prune sweep: temp_test of the model with the lowest units masked out of the first
