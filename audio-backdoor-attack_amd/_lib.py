@@ -36,6 +36,9 @@ EXPORTS = (
     "abd_reinit_weights_f32", "abd_smallcnn_unlearn_run", "abd_nwc_pair_f32",
     "abd_smallcnn_hidden_sums", "abd_smallcnn_fcprune_workspace_bytes", "abd_smallcnn_fcprune_eval",
     "abd_smallcnn_pruned_finetune_workspace_bytes", "abd_smallcnn_pruned_finetune_step",
+    "abd_lstmattn_create", "abd_lstmattn_destroy", "abd_lstmattn_param_count", "abd_lstmattn_param_offsets",
+    "abd_lstmattn_tile_rows", "abd_lstmattn_workspace_bytes", "abd_lstmattn_workspace_offset", "abd_lstmattn_forward",
+    "abd_lstmattn_backward", "abd_lstmattn_train_step", "abd_lstmattn_eval",
     "abd_profile_start", "abd_profile_start_every", "abd_profile_step", "abd_profile_stop",
 )
 
@@ -87,6 +90,21 @@ class TrainArgs(C.Structure):
         ("metrics", C.c_void_p), ("grad_scale", C.c_float), ("num_batches_tracked", C.c_void_p),
         ("fc_grads_event", C.c_void_p), ("row_offset", C.c_int64),
         ("bn_sync_buf", C.c_void_p), ("bn_sync", C.c_void_p), ("bn_sync_ctx", C.c_void_p),
+    ]
+
+
+class LstmAttnArgs(C.Structure):
+    """abd_lstmattn_args: abd_train_args without the second mask and the DP / SyncBN fields."""
+    _fields_ = [
+        ("x", C.c_void_p), ("labels", C.c_void_p), ("indicators", C.c_void_p), ("batch", C.c_int64),
+        ("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("running", C.c_void_p), ("adam_step", C.c_int64),
+        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("do_update", C.c_int),
+        ("mask_in", C.c_void_p), ("seed", C.c_uint64), ("counter", C.c_uint64),
+        ("mask_out", C.c_void_p), ("logits_out", C.c_void_p),
+        ("metrics", C.c_void_p), ("grad_scale", C.c_float), ("num_batches_tracked", C.c_void_p),
+        ("row_offset", C.c_int64),
     ]
 
 
@@ -233,6 +251,17 @@ def _declare(lib):
         "abd_smallcnn_fcprune_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
         "abd_smallcnn_pruned_finetune_workspace_bytes": (sz, [vp, i64]),
         "abd_smallcnn_pruned_finetune_step": (i32, [vp, C.POINTER(PrunedFinetuneArgs), vp, sz, vp]),
+        "abd_lstmattn_create": (i32, [i32, i32, i32, C.POINTER(vp)]),
+        "abd_lstmattn_destroy": (None, [vp]),
+        "abd_lstmattn_param_count": (i64, [vp]),
+        "abd_lstmattn_param_offsets": (i32, [vp, C.POINTER(i64)]),
+        "abd_lstmattn_tile_rows": (i32, []),
+        "abd_lstmattn_workspace_bytes": (sz, [vp, i64]),
+        "abd_lstmattn_workspace_offset": (i64, [vp, i64, C.c_char_p]),
+        "abd_lstmattn_forward": (i32, [vp, C.POINTER(LstmAttnArgs), i32, vp, sz, vp]),
+        "abd_lstmattn_backward": (i32, [vp, C.POINTER(LstmAttnArgs), vp, vp, sz, vp]),
+        "abd_lstmattn_train_step": (i32, [vp, C.POINTER(LstmAttnArgs), vp, sz, vp]),
+        "abd_lstmattn_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "abd_profile_start": (i32, [C.c_ulonglong, i32]),
         "abd_profile_start_every": (i32, [C.c_ulonglong, i32, i32]),
         "abd_profile_step": (i32, []),

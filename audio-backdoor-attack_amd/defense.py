@@ -42,6 +42,7 @@ def neuron_names(model=None, layer_type="conv"):
     if layer_type not in L.ABLATE_KINDS:
         raise SystemError("NO valid layer_type match!")   # the reference's own error
     if model is not None:
+        _refuse_lstm(model)
         kind = torch.nn.Conv2d if layer_type == "conv" else torch.nn.BatchNorm2d
         layers = [(n, m.weight.shape[0]) for n, m in model.named_modules() if isinstance(m, kind) and "shortcut" not in n]
     else:
@@ -95,10 +96,20 @@ def combine(loss_sums, sizes, correct, n: int):
     return loss, acc
 
 
+def _refuse_lstm(model, what="the defences"):
+    """The defences are smallcnn's (conv1..conv3 / bn1..bn3 / fc1 / fc2 and the abd_smallcnn_* entry points):
+    lstmwithattention, whose engine looks alike but whose flat buffers are laid out differently, is refused;
+    every other module is treated as before."""
+    from .models_lstm import lstmwithattention
+    if isinstance(model, lstmwithattention):
+        raise L.AbdError(f"{what} run the abd_amd smallcnn only, got lstmwithattention (DESIGN.md §5)")
+
+
 def _flat_state(model, device):
     """The model's parameters and BN running statistics as the C ABI's flat fp32 buffers: the bound
     engine's own buffers when the model already lives in them, else packed copies of the VALUES (the
     module itself is left as it is -- no re-homing, no mode change)."""
+    _refuse_lstm(model)
     eng = getattr(model, "_engine", None)
     if eng is not None and eng.device == device and model._bound(eng):
         return eng.params, eng.running
@@ -219,6 +230,7 @@ def final_gradients(model):
     """``p.grad``-style views of the engine's flat gradient buffer, in parameter order; also installed as
     the parameters' .grad (the reference assigns ``param.grad = grad``, ft_reg.py:110-112)."""
     from . import training as T
+    _refuse_lstm(model)
     T.expose_grads(model)
     return [p.grad for p in model._param_list()]
 
@@ -299,6 +311,7 @@ UCN_HEAD = "No \t Layer_Name \t Neuron_Idx \t Score \n"
 
 def param_offsets(model):
     """Element offsets of the 16 parameter tensors inside the flat buffers (17 entries, parameter order)."""
+    _refuse_lstm(model)
     d = dict(model.named_parameters())
     offs = [0]
     for n in PARAM_ORDER:
@@ -324,6 +337,7 @@ def row_table(model, layer_type="conv"):
 
 def _adam_binding(model, optimizer, what):
     from . import training as T
+    _refuse_lstm(model, what)
     if not T.fusable(model, optimizer, torch.nn.CrossEntropyLoss()):
         raise L.AbdError(f"{what}: this optimizer is not the device Adam step's (torch.optim.Adam, one param group "
                          "over the model's parameters, no weight decay / amsgrad / maximize)")

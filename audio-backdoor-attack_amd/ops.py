@@ -746,3 +746,91 @@ def _(x, labels, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracke
       mask2_out, num_classes, adam_step, lr, beta1, beta2, eps, seed, counter, mask1_in=None, mask2_in=None,
       precision="f32split", row_offset=0):
     return x.new_empty((x.shape[0], num_classes))
+
+
+# --------------------------------------------------------------------------- lstmwithattention
+_LSTM_NETS: dict = {}
+
+
+def _lstm_net(T: int, F: int, K: int):
+    """A cached libabd lstmwithattention handle for one geometry (shapes only, no device state)."""
+    key = (int(T), int(F), int(K))
+    h = _LSTM_NETS.get(key)
+    if h is None:
+        h = C.c_void_p()
+        L.check(L.lib().abd_lstmattn_create(key[0], key[1], key[2], C.byref(h)), "abd_lstmattn_create")
+        _LSTM_NETS[key] = h
+    return h
+
+
+def _lstm_eval(x, params, running, num_classes, labels, indicators, metrics):
+    L.require_device(x, "lstmwithattention input")
+    B, T, F = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    h = _lstm_net(T, F, num_classes)
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
+    ws = _ws(L.lib().abd_lstmattn_workspace_bytes(h, B), x.device)
+    L.check(L.lib().abd_lstmattn_eval(h, x.data_ptr(), B, params.data_ptr(), running.data_ptr(), _ptr(labels),
+                                      _ptr(indicators), out.data_ptr(), _ptr(metrics), ws.data_ptr(), ws.numel(),
+                                      L.stream_ptr(x.device)), "abd_lstmattn_eval")
+    return out
+
+
+@torch.library.custom_op("abd::lstmattn_eval", mutates_args=())
+def lstmattn_eval(x: Tensor, params: Tensor, running: Tensor, num_classes: int) -> Tensor:
+    """model.eval() forward of lstmwithattention: (B, 1, T, F) -> logits (B, K); running BN statistics,
+    no dropout."""
+    return _lstm_eval(x, params, running, num_classes, None, None, None)
+
+
+@lstmattn_eval.register_fake
+def _(x, params, running, num_classes):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::lstmattn_eval_metrics", mutates_args=("metrics",))
+def lstmattn_eval_metrics(x: Tensor, params: Tensor, running: Tensor, num_classes: int, labels: Tensor,
+                          indicators: Optional[Tensor], metrics: Tensor) -> Tensor:
+    """The eval forward plus test()'s loss / accuracy / ASR counters accumulated into metrics
+    (int64[8]); returns the logits."""
+    return _lstm_eval(x, params, running, num_classes, labels, indicators, metrics)
+
+
+@lstmattn_eval_metrics.register_fake
+def _(x, params, running, num_classes, labels, indicators, metrics):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::lstmattn_train_step",
+                         mutates_args=("params", "grads", "exp_avg", "exp_avg_sq", "running", "num_batches_tracked",
+                                       "metrics"))
+def lstmattn_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor], params: Tensor, grads: Tensor,
+                        exp_avg: Tensor, exp_avg_sq: Tensor, running: Tensor, num_batches_tracked: Tensor,
+                        metrics: Tensor, num_classes: int, adam_step: int, lr: float, beta1: float, beta2: float,
+                        eps: float, seed: int, counter: int, mask: Optional[Tensor] = None) -> Tensor:
+    """One fused train() iteration of lstmwithattention on the device; returns the batch's logits (B, K).
+    adam_step >= 1 applies torch.optim.Adam (that step index); 0 leaves params untouched."""
+    L.require_device(x, "lstmwithattention input")
+    B, T, F = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    h = _lstm_net(T, F, num_classes)
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
+    a = L.LstmAttnArgs()
+    a.x, a.batch = x.data_ptr(), B
+    a.labels, a.indicators = labels.data_ptr(), _ptr(indicators)
+    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
+    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    a.num_batches_tracked = num_batches_tracked.data_ptr()
+    a.lr, a.beta1, a.beta2, a.eps = float(lr), float(beta1), float(beta2), float(eps)
+    a.adam_step, a.do_update = int(adam_step), 1 if adam_step > 0 else 0
+    a.seed, a.counter = int(seed), int(counter)
+    a.mask_in = _ptr(mask)
+    a.logits_out, a.metrics, a.grad_scale = out.data_ptr(), metrics.data_ptr(), 1.0
+    ws = _ws(L.lib().abd_lstmattn_workspace_bytes(h, B), x.device)
+    L.check(L.lib().abd_lstmattn_train_step(h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
+            "abd_lstmattn_train_step")
+    return out
+
+
+@lstmattn_train_step.register_fake
+def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics, num_classes,
+      adam_step, lr, beta1, beta2, eps, seed, counter, mask=None):
+    return x.new_empty((x.shape[0], num_classes))

@@ -203,6 +203,7 @@ class ResidentTrainer:
         collectives: run the data-parallel step (overlapped gradient all-reduce, SyncBN, separate
         Adam) -- default world > 1; True at world 1 drives the same collectives over a one-rank
         group (tests/test_gpu_rccl.py runs them through RCCL on a single GPU)."""
+        T.require_smallcnn(model, "ResidentTrainer (the HBM-resident / data-parallel / SyncBN loop)")
         assert waves.is_cuda and waves.dtype == torch.float32 and waves.dim() == 2
         self.cfg, self.model, self.opt = cfg, model, optimizer
         self.B, self.rank, self.world, self.pg = int(batch_size), rank, world, process_group

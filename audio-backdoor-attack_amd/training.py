@@ -20,14 +20,27 @@ import torch.nn as nn
 
 from . import _lib as L
 from .models import smallcnn, dropout_seed
+from .models_lstm import lstmwithattention
 from .resident import resident_batches
+
+# the models whose train() / test() steps run on libabd
+ACCELERATED = (smallcnn, lstmwithattention)
+
+
+def require_smallcnn(model, what: str):
+    """Raise AbdError unless model is the abd_amd smallcnn: the data-parallel / SyncBN trainer, the direct
+    smallcnn step and the defences drive the abd_smallcnn_* entry points, whose handle and flat buffer layout
+    are smallcnn's own (lstmwithattention has the same Python surface but another layout)."""
+    if not isinstance(model, smallcnn):
+        raise L.AbdError(f"{what} runs the abd_amd smallcnn only, got {type(model).__name__}")
 
 
 # ------------------------------------------------------------------ Adam state shared with torch
 class AdamBinding:
-    """Flat exp_avg / exp_avg_sq buffers exposed to the torch optimizer as per-param views."""
+    """Flat exp_avg / exp_avg_sq buffers exposed to the torch optimizer as per-param views (either
+    accelerated model: both keep a flat parameter buffer and the same engine surface)."""
 
-    def __init__(self, model: smallcnn, optimizer: torch.optim.Optimizer):
+    def __init__(self, model: smallcnn | lstmwithattention, optimizer: torch.optim.Optimizer):
         eng = model._engine
         self.model, self.opt = model, optimizer
         g = optimizer.param_groups[0]
@@ -100,7 +113,7 @@ def check_sgd(model, optimizer):
 
 
 def fusable(model, optimizer, criterion) -> bool:
-    if not isinstance(model, smallcnn) or not isinstance(optimizer, torch.optim.Adam):
+    if not isinstance(model, ACCELERATED) or not isinstance(optimizer, torch.optim.Adam):
         return False
     if len(optimizer.param_groups) != 1:
         return False
@@ -145,7 +158,9 @@ def train_step(model: smallcnn, x, labels, indicators, adam: AdamBinding | None,
     """One fused device step (forward + CE + backward [+ Adam]) -- the per-batch hot path.
 
     row_offset: global batch row of x[0] (data parallelism: dropout masks hash the global row).
-    bn_sync: a parallel_dp.SyncBatchNorm (synchronised BatchNorm statistics) or None."""
+    bn_sync: a parallel_dp.SyncBatchNorm (synchronised BatchNorm statistics) or None.
+    smallcnn only (lstmwithattention: lstm_train_step; it has no data-parallel / SyncBN step)."""
+    require_smallcnn(model, "train_step (the smallcnn / data-parallel step)")
     eng = model.engine(x)
     B = x.shape[0]
     a = model._args(eng, x, B)
@@ -184,10 +199,57 @@ def train_step(model: smallcnn, x, labels, indicators, adam: AdamBinding | None,
     return a
 
 
-def op_train_step(model: smallcnn, x, labels, indicators, adam: AdamBinding, metrics: torch.Tensor):
-    """train()'s per-batch step through the ``abd::smallcnn_train_step`` custom op (ops.py)."""
+def lstm_train_step(model: lstmwithattention, x, labels, indicators, adam: AdamBinding | None,
+                    metrics: torch.Tensor | None, mask=None, mask_out=None, do_update=True, grad_scale=1.0, seed=None,
+                    logits_out=None):
+    """One fused device step of lstmwithattention (forward + CE + backward [+ Adam]) through the C ABI."""
+    eng = model.engine(x)
+    B = x.shape[0]
+    a = model._args(eng, x, B)
+    a.labels = labels.data_ptr() if labels is not None else None
+    a.indicators = indicators.data_ptr() if indicators is not None else None
+    if adam is not None:
+        a.exp_avg, a.exp_avg_sq = eng.exp_avg.data_ptr(), eng.exp_avg_sq.data_ptr()
+        a.lr, (a.beta1, a.beta2), a.eps = adam.lr, adam.betas, adam.eps
+        if do_update:
+            adam.step += 1
+            a.adam_step = adam.step
+            a.do_update = 1
+    a.seed = dropout_seed(x.device, model) if seed is None else seed
+    a.counter = model._step
+    model._step += 1
+    if mask is None:
+        mask = model.step_mask(B, x.device)
+    if mask is not None:
+        a.mask_in = mask.data_ptr()
+    if mask_out is not None:
+        a.mask_out = mask_out.data_ptr()
+    if metrics is not None:
+        a.metrics = metrics.data_ptr()
+    if logits_out is not None:
+        a.logits_out = logits_out.data_ptr()
+    a.grad_scale = float(grad_scale)
+    ws = eng.workspace(B)
+    rc = L.lib().abd_lstmattn_train_step(eng.h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
+    L.check(rc, "abd_lstmattn_train_step")
+    return a
+
+
+def op_train_step(model: smallcnn | lstmwithattention, x, labels, indicators, adam: AdamBinding,
+                  metrics: torch.Tensor):
+    """train()'s per-batch step through the model's custom op, ``abd::smallcnn_train_step`` or
+    ``abd::lstmattn_train_step`` (ops.py)."""
     from . import ops  # noqa: F401  (registers torch.ops.abd)
     eng = model.engine(x)
+    if isinstance(model, lstmwithattention):
+        hm = model.step_mask(x.shape[0], x.device)
+        adam.step += 1
+        torch.ops.abd.lstmattn_train_step(
+            x, labels, indicators, eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, eng.running, eng.nbt, metrics,
+            eng.K, adam.step, adam.lr, adam.betas[0], adam.betas[1], adam.eps, dropout_seed(x.device, model),
+            model._step, hm)
+        model._step += 1
+        return
     hm = model.step_masks(x.shape[0], x.device)
     adam.step += 1
     torch.ops.abd.smallcnn_train_step(
@@ -197,7 +259,7 @@ def op_train_step(model: smallcnn, x, labels, indicators, adam: AdamBinding, met
     model._step += 1
 
 
-def apply_adam(model: smallcnn, adam: AdamBinding, device):
+def apply_adam(model: smallcnn | lstmwithattention, adam: AdamBinding, device):
     eng = model._engine
     adam.step += 1
     rc = L.lib().abd_adam_f32(eng.params.data_ptr(), eng.grads.data_ptr(), eng.exp_avg.data_ptr(),
@@ -206,7 +268,7 @@ def apply_adam(model: smallcnn, adam: AdamBinding, device):
     L.check(rc, "abd_adam_f32")
 
 
-def expose_grads(model: smallcnn):
+def expose_grads(model: smallcnn | lstmwithattention):
     """p.grad views of the flat gradient buffer (what the reference sees after backward)."""
     eng = model._engine
     for p, g in zip(model._param_list(), eng.views(eng.grads)):
@@ -220,8 +282,8 @@ def read_metrics(m: torch.Tensor):
 
 
 def _unsupported(model):
-    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn + Adam + CrossEntropyLoss hot path only; got "
-                     f"{type(model).__name__} (other models are out of scope, see DESIGN.md)")
+    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn / lstmwithattention + Adam + CrossEntropyLoss "
+                     f"hot path only; got {type(model).__name__} (other models are out of scope, see DESIGN.md)")
 
 
 # ------------------------------------------------------------------ reference signatures
@@ -255,15 +317,18 @@ def _eval_batches(model, loader, dev, dict_items):
     n = 0
     for x, y, ind in _batches(loader, dev, dict_items):
         eng = model.engine(x)
-        torch.ops.abd.smallcnn_eval_metrics(x, eng.params, eng.running, eng.K, model.gemm_precision, y, ind,
-                                            metrics)
+        if isinstance(model, lstmwithattention):
+            torch.ops.abd.lstmattn_eval_metrics(x, eng.params, eng.running, eng.K, y, ind, metrics)
+        else:
+            torch.ops.abd.smallcnn_eval_metrics(x, eng.params, eng.running, eng.K, model.gemm_precision, y, ind,
+                                                metrics)
         n += 1
     return read_metrics(metrics), n
 
 
 def test(model, device, clean_test_loader, bd_test_loader, criterion):
     """utils/training_tools.py:87-134 -> (test_clean_acc, test_asr, clean_test_loss, bd_test_loss)."""
-    if not isinstance(model, smallcnn):
+    if not isinstance(model, ACCELERATED):
         _unsupported(model)
     model.eval()
     dev = torch.device(device) if not isinstance(device, torch.device) else device
@@ -297,7 +362,7 @@ def clean_train(model, train_loader, device, optimizer, criterion):
 
 def clean_test(model, device, clean_test_loader, criterion):
     """utils/training_tools.py:159-180 -> (test_loss, test_acc)."""
-    if not isinstance(model, smallcnn):
+    if not isinstance(model, ACCELERATED):
         _unsupported(model)
     model.eval()
     dev = torch.device(device) if not isinstance(device, torch.device) else device
@@ -346,7 +411,7 @@ class _GlobalPickleModule:
         return getattr(pickle, k)
 
 
-def reference_module_state(model: smallcnn) -> dict:
+def reference_module_state(model: smallcnn | lstmwithattention) -> dict:
     """``__dict__`` of the reference's ``utils.models.smallcnn`` (utils/models.py:17-40) holding this
     model's parameters and BN buffers: plain nn.Module bookkeeping and the same children in the same
     order (Conv2d / BatchNorm2d / MaxPool2d / Dropout / Flatten / Linear / Softmax()), each with its
@@ -364,7 +429,7 @@ def reference_module_state(model: smallcnn) -> dict:
     return ref.__dict__.copy()
 
 
-def reference_pickle_object(model: smallcnn, module: str = "utils.models", name: str = "smallcnn"):
+def reference_pickle_object(model: smallcnn | lstmwithattention, module: str = "utils.models", name: str = "smallcnn"):
     """An object that pickles exactly as the reference's ``torch.save(model)`` pickles its
     ``utils.models.smallcnn`` (utils/training_tools.py:49): protocol 2's ``GLOBAL utils.models
     smallcnn`` + ``NEWOBJ`` + ``BUILD`` of the module ``__dict__`` (reference_module_state).
@@ -380,10 +445,13 @@ def reference_pickle_object(model: smallcnn, module: str = "utils.models", name:
 
 
 def save_reference_checkpoint(model, path):
-    """torch.save in the reference's format: abd smallcnn -> a utils.models.smallcnn pickle; any other
-    module is saved as is (the reference's behaviour)."""
+    """torch.save in the reference's format: abd smallcnn / lstmwithattention -> a pickle of the
+    utils.models class of the same name; any other module is saved as is (the reference's behaviour)."""
     if isinstance(model, smallcnn):
         torch.save(reference_pickle_object(model), path, pickle_module=_GlobalPickleModule())
+    elif isinstance(model, lstmwithattention):
+        torch.save(reference_pickle_object(model, name="lstmwithattention"), path,
+                   pickle_module=_GlobalPickleModule())
     else:
         torch.save(model, path)
 

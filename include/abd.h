@@ -702,6 +702,84 @@ int abd_profile_start_every(unsigned long long phase_mask, int max_records, int 
 int abd_profile_step(void);
 int abd_profile_stop(double* total_ms, int* counts, int n_phases);
 
+/* ------------------------------------------------------------------ lstmwithattention
+ * Replaces utils/models.py:180-228 lstmwithattention(classes, time_len, seq_len) forward / backward
+ * and the train() / test() inner steps for it.  Input (B, 1, T, F) fp32 with T = seq_len,
+ * F = time_len; the module returns raw logits (nn.CrossEntropyLoss does the log-softmax).
+ *
+ * Parameters live in ONE flat fp32 buffer in named_parameters() order, 34 tensors: conv1.w/b,
+ * batchnorm1.w/b, conv2.w/b, batchnorm2.w/b, rnn1 {weight_ih, weight_hh, bias_ih, bias_hh}_l0 and the
+ * four _reverse ones, the same eight of rnn2, then dense1, attention, dense2, dense3, output (.w, .b).
+ * running: rm1[10] rv1[10] rm2[1] rv2[1]; num_batches_tracked: int64[2].
+ *
+ * Every product is fp32 (v_mfma_f32_32x32x2_f32 GEMMs, fp32 FMAs in the recurrence); there is no
+ * bf16 mode.  Each LSTM layer's recurrence is one launch whose workgroups keep W_hh of their
+ * direction in LDS for all T steps (abd_lstmattn_tile_rows() batch rows per workgroup).  All
+ * reductions have a fixed order: two calls on equal inputs give bit-equal results.  The entry points
+ * allocate nothing, never synchronise and take nothing from host memory but their arguments. */
+typedef struct abd_lstmattn abd_lstmattn;
+
+typedef struct abd_lstmattn_args {
+  const float* x;            /* (B,1,T,F)                                      */
+  const int64_t* labels;     /* (B)                                            */
+  const int64_t* indicators; /* (B) poison indicator, NULL = none              */
+  int64_t batch;
+  float* params;             /* flat                                           */
+  float* grads;              /* flat (written)                                 */
+  float* exp_avg;            /* flat Adam m                                    */
+  float* exp_avg_sq;         /* flat Adam v                                    */
+  float* running;            /* 22 floats                                      */
+  int64_t adam_step;         /* step index after increment (1-based)           */
+  float lr, beta1, beta2, eps;
+  int do_update;             /* 0: forward/backward only (grads), 1: + Adam    */
+  const uint8_t* mask_in;    /* optional dropout keep mask (B,64); NULL ->
+                              * generated from (seed, counter, global row)     */
+  uint64_t seed, counter;
+  uint8_t* mask_out;         /* optional: the mask used                        */
+  float* logits_out;         /* optional (B,K)                                 */
+  int64_t* metrics;          /* optional ABD_METRICS_WORDS accumulators        */
+  float grad_scale;          /* multiplies the loss gradient and weights
+                              * metrics[0]'s batch-mean loss                   */
+  int64_t* num_batches_tracked; /* optional int64[2], += 1 per train forward   */
+  int64_t row_offset;        /* global batch row of row 0 (dropout hash)       */
+} abd_lstmattn_args;
+
+/* ABD_E_UNSUPPORTED outside 1 <= F <= 128, 1 <= T <= 1024 */
+int abd_lstmattn_create(int T, int F, int num_classes, abd_lstmattn** net);
+void abd_lstmattn_destroy(abd_lstmattn* net);
+int64_t abd_lstmattn_param_count(const abd_lstmattn* net);
+int abd_lstmattn_param_offsets(const abd_lstmattn* net, int64_t* offsets /* 35 */);
+/* batch rows one workgroup of the recurrent kernels carries through the sequence */
+int abd_lstmattn_tile_rows(void);
+size_t abd_lstmattn_workspace_bytes(const abd_lstmattn* net, int64_t batch);
+/* Byte offset of a saved activation inside the workspace (tests), -1 for an unknown name:
+ * a1 a2 x0 (conv / BatchNorm outputs), y1 y2 ((B,T,128) h_t of rnn1 / rnn2, forward | reverse half),
+ * c1 c2 ([2][B][T][64] cell states), gates1 gates2 ([2][B][T][256] activated i f g o), q att av d2 d3
+ * logits dlogits mask rowinfo dy2 dy1 dx0. */
+int64_t abd_lstmattn_workspace_offset(const abd_lstmattn* net, int64_t batch, const char* name);
+/* forward keeps every activation in the workspace and writes the logits to a->logits_out (if set);
+ * train_mode selects batch statistics + dropout (running statistics updated) vs running statistics.
+ * backward consumes d(logits) and must follow a train-mode forward on the same workspace.
+ * Train mode needs B*T*F > 1 (BatchNorm over one value has no variance; torch raises too), else
+ * ABD_E_INVALID. */
+int abd_lstmattn_forward(abd_lstmattn* net, const abd_lstmattn_args* a, int train_mode, void* workspace,
+                         size_t workspace_bytes, abd_stream_t stream);
+int abd_lstmattn_backward(abd_lstmattn* net, const abd_lstmattn_args* a, const float* dlogits,
+                          void* workspace, size_t workspace_bytes, abd_stream_t stream);
+/* forward, cross entropy on the logits (mean over the batch) with the ABD_METRICS_WORDS counters as
+ * abd_smallcnn_train_step defines them, backward, and abd_adam_f32 on the flat buffer when do_update.
+ * labels are required (ABD_E_INVALID).  The step's d(logits) follows the arithmetic of torch's
+ * log_softmax / nll_loss backward (its exp and log routines, its reduction order for K <= 64), so the
+ * autograd path -- forward, torch's CrossEntropyLoss, backward -- gives bit-equal gradients. */
+int abd_lstmattn_train_step(abd_lstmattn* net, const abd_lstmattn_args* a, void* workspace,
+                            size_t workspace_bytes, abd_stream_t stream);
+/* eval forward: running statistics, no dropout.  Writes the logits and, if labels != NULL,
+ * accumulates the counters like test(). */
+int abd_lstmattn_eval(abd_lstmattn* net, const float* x, int64_t batch, const float* params,
+                      const float* running, const int64_t* labels, const int64_t* indicators,
+                      float* logits, int64_t* metrics, void* workspace, size_t workspace_bytes,
+                      abd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

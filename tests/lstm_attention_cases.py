@@ -1,0 +1,266 @@
+"""Fixture of the lstmwithattention tests: deterministic cases and a float64 restatement of the model.
+
+Per case (numpy-seeded): a full parameter / buffer set under the reference's state_dict names, an
+MFCC-scale input (sigma ~ 20), labels, poison indicators and a dropout keep-mask.  LSTM and dense
+weights are drawn about three times wider than torch's default U(-1/sqrt(fan), 1/sqrt(fan)), so the gate
+pre-activations reach the saturating range: a wrong gate order or a dropped bias cannot hide in the
+linear regime.  The BatchNorm running statistics are drawn near the true scale of the activations, so the
+eval-mode LSTM input is O(1) as well.
+
+``Restated`` restates utils/models.py:180-228 from torch CPU primitives (conv2d, batch_norm, nn.LSTM,
+linear, softmax, einsum) with the dropout mask as an input; ``lstm_states`` unrolls one bidirectional layer
+step by step for the per-step h / c the device saves; ``adam_step`` is one torch.optim.Adam update.  In
+float64 this is the oracle of the GPU tests (the reference checkout is not on the GPU machine);
+tests/test_lstm_attention_cpu.py ties it to the reference's own module through
+tests/golden/lstm_attention_golden.npz.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+TILE = 8   # batch rows per workgroup of the recurrent kernels (abd_lstmattn_tile_rows)
+
+# name -> (B, T, F, K, seed).  The seeds are picked so that the float32 restatement stays within 1e-5 of the
+# float64 one and every row's top-2 logit gap exceeds 1e-3 (asserted in tests/test_lstm_attention_cpu.py).
+CASES = {
+    "tiny": (3, 7, 13, 10, 21),            # T barely above the conv kernel, F % 4 != 0, B below a tile
+    "one_row": (1, 32, 13, 10, 12),        # BatchNorm on one row
+    "ragged_tiles": (2 * TILE + 1, 32, 13, 35, 21),   # two full batch tiles plus a ragged one
+    "long": (5, 101, 40, 10, 14),          # odd T, the longest recurrence
+}
+
+_RNN = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
+        "weight_ih_l0_reverse", "weight_hh_l0_reverse", "bias_ih_l0_reverse", "bias_hh_l0_reverse")
+PARAM_ORDER = (
+    "conv1.weight", "conv1.bias", "batchnorm1.weight", "batchnorm1.bias",
+    "conv2.weight", "conv2.bias", "batchnorm2.weight", "batchnorm2.bias",
+    *[f"rnn1.{n}" for n in _RNN], *[f"rnn2.{n}" for n in _RNN],
+    "dense1.weight", "dense1.bias", "attention.weight", "attention.bias", "dense2.weight", "dense2.bias",
+    "dense3.weight", "dense3.bias", "output.weight", "output.bias",
+)
+BUFFERS = ("batchnorm1.running_mean", "batchnorm1.running_var", "batchnorm1.num_batches_tracked",
+           "batchnorm2.running_mean", "batchnorm2.running_var", "batchnorm2.num_batches_tracked")
+WIDEN = 3.0
+LR, BETAS, EPS = 1e-3, (0.9, 0.999), 1e-8
+SAMPLE_STRIDE = 37    # gradient tensors above 4096 elements are stored as flat[::SAMPLE_STRIDE]
+
+
+def param_shapes(T, Fd, K):
+    s = {"conv1.weight": (10, 1, 5, 1), "conv1.bias": (10,), "batchnorm1.weight": (10,), "batchnorm1.bias": (10,),
+         "conv2.weight": (1, 10, 5, 1), "conv2.bias": (1,), "batchnorm2.weight": (1,), "batchnorm2.bias": (1,)}
+    for rnn, inp in (("rnn1", Fd), ("rnn2", 128)):
+        for suf in ("", "_reverse"):
+            s[f"{rnn}.weight_ih_l0{suf}"] = (256, inp)
+            s[f"{rnn}.weight_hh_l0{suf}"] = (256, 64)
+            s[f"{rnn}.bias_ih_l0{suf}"] = (256,)
+            s[f"{rnn}.bias_hh_l0{suf}"] = (256,)
+    s.update({"dense1.weight": (128, 128), "dense1.bias": (128,), "attention.weight": (128, 128),
+              "attention.bias": (128,), "dense2.weight": (64, T), "dense2.bias": (64,), "dense3.weight": (32, 64),
+              "dense3.bias": (32,), "output.weight": (K, 32), "output.bias": (K,)})
+    return {n: s[n] for n in PARAM_ORDER}
+
+
+def make_state(name):
+    """The case's state_dict as numpy arrays (float32 parameters / statistics, int64 counters)."""
+    B, T, Fd, K, seed = CASES[name]
+    r = np.random.Generator(np.random.PCG64(1000 + seed))
+    st = {}
+    for n, shp in param_shapes(T, Fd, K).items():
+        mod, leaf = n.split(".", 1)
+        if mod.startswith("batchnorm"):
+            v = r.uniform(0.5, 1.5, shp) if leaf == "weight" else r.normal(0.0, 0.3, shp)
+        elif mod.startswith("conv"):
+            fan = 5 if mod == "conv1" else 50
+            v = r.uniform(-1, 1, shp) / np.sqrt(fan)
+        elif mod.startswith("rnn"):
+            v = WIDEN * r.uniform(-1, 1, shp) / 8.0
+        else:
+            fan = shp[1] if leaf == "weight" else {"dense1": 128, "attention": 128, "dense2": T, "dense3": 64,
+                                                    "output": 32}[mod]
+            v = WIDEN * r.uniform(-1, 1, shp) / np.sqrt(fan)
+        st[n] = v.astype(np.float32)
+    st["batchnorm1.running_mean"] = r.normal(6.0, 2.0, 10).astype(np.float32)
+    st["batchnorm1.running_var"] = r.uniform(60.0, 160.0, 10).astype(np.float32)
+    st["batchnorm1.num_batches_tracked"] = np.array(3, dtype=np.int64)
+    st["batchnorm2.running_mean"] = r.normal(1.0, 0.3, 1).astype(np.float32)
+    st["batchnorm2.running_var"] = r.uniform(1.0, 2.0, 1).astype(np.float32)
+    st["batchnorm2.num_batches_tracked"] = np.array(5, dtype=np.int64)
+    return st
+
+
+def make_inputs(name):
+    """x (B,1,T,F) float32, labels, indicators (int64), dropout keep-mask (B,64) uint8."""
+    B, T, Fd, K, seed = CASES[name]
+    r = np.random.Generator(np.random.PCG64(2000 + seed))
+    x = (20.0 * r.normal(size=(B, 1, T, Fd))).astype(np.float32)
+    y = r.integers(0, K, B).astype(np.int64)
+    ind = (r.uniform(size=B) < 0.4).astype(np.int64)
+    mask = (r.uniform(size=(B, 64)) < 0.5).astype(np.uint8)
+    return x, y, ind, mask
+
+
+class Restated(nn.Module):
+    """utils/models.py:180-228 from torch primitives; the dropout keep-mask is an argument."""
+
+    def __init__(self, state, dtype=torch.float64):
+        super().__init__()
+        T = state["dense2.weight"].shape[1]
+        Fd = state["rnn1.weight_ih_l0"].shape[1]
+        self.rnn1 = nn.LSTM(input_size=Fd, hidden_size=64, bidirectional=True, batch_first=True)
+        self.rnn2 = nn.LSTM(input_size=128, hidden_size=64, bidirectional=True, batch_first=True)
+        self.p = nn.ParameterDict()
+        for n in PARAM_ORDER:
+            t = torch.tensor(np.asarray(state[n]), dtype=dtype)
+            if n.startswith("rnn"):
+                continue
+            self.p[n.replace(".", "__")] = nn.Parameter(t)
+        self.to(dtype)
+        with torch.no_grad():
+            for n in PARAM_ORDER:
+                if n.startswith("rnn"):
+                    mod, leaf = n.split(".", 1)
+                    getattr(getattr(self, mod), leaf).copy_(torch.tensor(np.asarray(state[n]), dtype=dtype))
+        for n in BUFFERS:
+            t = torch.tensor(np.asarray(state[n]))
+            self.register_buffer(n.replace(".", "__"), t.to(dtype) if t.is_floating_point() else t)
+        self.T = T
+
+    def named(self, n):
+        if n.startswith("rnn"):
+            mod, leaf = n.split(".", 1)
+            return getattr(getattr(self, mod), leaf)
+        return self.p[n.replace(".", "__")]
+
+    def buf(self, n):
+        return getattr(self, n.replace(".", "__"))
+
+    def forward(self, x, train, mask=None, keep=None):
+        """logits; keep: optional dict that receives the intermediate tensors."""
+        g = self.named
+        x = torch.relu(F.conv2d(x, g("conv1.weight"), g("conv1.bias"), padding=(2, 0)))
+        if train:
+            self.batchnorm1__num_batches_tracked += 1
+            self.batchnorm2__num_batches_tracked += 1
+        x = F.batch_norm(x, self.buf("batchnorm1.running_mean"), self.buf("batchnorm1.running_var"),
+                         g("batchnorm1.weight"), g("batchnorm1.bias"), train, 0.1, 1e-5)
+        x = torch.relu(F.conv2d(x, g("conv2.weight"), g("conv2.bias"), padding=(2, 0)))
+        x = F.batch_norm(x, self.buf("batchnorm2.running_mean"), self.buf("batchnorm2.running_var"),
+                         g("batchnorm2.weight"), g("batchnorm2.bias"), train, 0.1, 1e-5)
+        x0 = x.squeeze(1)
+        y1, _ = self.rnn1(x0)
+        y2, _ = self.rnn2(y1)
+        query = torch.relu(F.linear(y2[:, -1], g("dense1.weight"), g("dense1.bias")))
+        att = F.softmax(F.linear(query, g("attention.weight"), g("attention.bias")), dim=1)
+        av = torch.einsum("ik,ijk->ij", att, y2)
+        d2 = torch.relu(F.linear(av, g("dense2.weight"), g("dense2.bias")))
+        if train:
+            d2 = d2 * (mask.to(d2.dtype) * 2.0)
+        d3 = torch.relu(F.linear(d2, g("dense3.weight"), g("dense3.bias")))
+        if keep is not None:
+            keep.update(x0=x0, y1=y1, y2=y2)
+        return F.linear(d3, g("output.weight"), g("output.bias"))
+
+    def grads(self):
+        return {n: self.named(n).grad.detach().clone() for n in PARAM_ORDER}
+
+    def params(self):
+        return {n: self.named(n).detach().clone() for n in PARAM_ORDER}
+
+
+def lstm_states(x, rnn):
+    """Unroll one bidirectional nn.LSTM layer: (h, c), each (2, B, T, 64), direction 1 stored at the
+    position t it was computed for (torch semantics: gate rows i f g o, reverse runs T-1 .. 0)."""
+    B, T, _ = x.shape
+    hs, cs = [], []
+    for suf in ("", "_reverse"):
+        wi, wh = getattr(rnn, "weight_ih_l0" + suf), getattr(rnn, "weight_hh_l0" + suf)
+        b = getattr(rnn, "bias_ih_l0" + suf) + getattr(rnn, "bias_hh_l0" + suf)
+        h = x.new_zeros((B, 64))
+        c = x.new_zeros((B, 64))
+        hrow, crow = [None] * T, [None] * T
+        for t in (range(T) if suf == "" else range(T - 1, -1, -1)):
+            z = x[:, t] @ wi.T + h @ wh.T + b
+            i, f, g, o = torch.sigmoid(z[:, :64]), torch.sigmoid(z[:, 64:128]), torch.tanh(z[:, 128:192]), \
+                torch.sigmoid(z[:, 192:])
+            c = f * c + i * g
+            h = o * torch.tanh(c)
+            hrow[t], crow[t] = h, c
+        hs.append(torch.stack(hrow, 1))
+        cs.append(torch.stack(crow, 1))
+    return torch.stack(hs), torch.stack(cs)
+
+
+def adam_step(p, g, step=1, m=None, v=None, lr=LR, betas=BETAS, eps=EPS):
+    """torch.optim.Adam (weight_decay 0) on one float64 tensor; returns (p, m, v)."""
+    m = torch.zeros_like(p) if m is None else m
+    v = torch.zeros_like(p) if v is None else v
+    m = betas[0] * m + (1 - betas[0]) * g
+    v = betas[1] * v + (1 - betas[1]) * g * g
+    bc1, bc2 = 1 - betas[0] ** step, 1 - betas[1] ** step
+    return p - (lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + eps), m, v
+
+
+_CACHE: dict = {}
+
+
+def run_case(name, dtype=torch.float64):
+    """Everything the tests compare against, computed once per (case, dtype) and shared (read only):
+    eval / train logits, loss, gradients, running statistics after the train forward, saved states,
+    row losses of the eval pass and the parameters after one Adam step."""
+    key = (name, dtype)
+    if key in _CACHE:
+        return _CACHE[key]
+    st = make_state(name)
+    x, y, ind, mask = make_inputs(name)
+    xt, yt, mt = torch.tensor(x, dtype=dtype), torch.tensor(y), torch.tensor(mask)
+    out = {}
+    m = Restated(st, dtype)
+    with torch.no_grad():
+        out["eval_logits"] = m(xt, False)
+        out["eval_loss"] = F.cross_entropy(out["eval_logits"], yt)
+    keep = {}
+    logits = m(xt, True, mt, keep)
+    loss = F.cross_entropy(logits, yt)
+    loss.backward()
+    out["train_logits"], out["loss"] = logits.detach(), loss.detach()
+    out["grads"] = m.grads()
+    out["running"] = {n: m.buf(n).detach().clone() for n in BUFFERS}
+    with torch.no_grad():
+        out["h1"], out["c1"] = lstm_states(keep["x0"].detach(), m.rnn1)
+        out["h2"], out["c2"] = lstm_states(keep["y1"].detach(), m.rnn2)
+        out["y1"], out["y2"] = keep["y1"].detach(), keep["y2"].detach()
+        out["adam"] = {n: adam_step(p, out["grads"][n])[0] for n, p in m.params().items()}
+    _CACHE[key] = out
+    return out
+
+
+def rel_err(a, b):
+    """max |a - b| relative to the largest magnitude of the reference b."""
+    a = torch.as_tensor(a, dtype=torch.float64).reshape(-1)
+    b = torch.as_tensor(b, dtype=torch.float64).reshape(-1)
+    d = float((a - b).abs().max())
+    s = float(b.abs().max())
+    return d / s if s > 0 else d
+
+
+def sample(t):
+    """What the golden file stores of a gradient tensor: all of it up to 4096 elements, else a stride sample."""
+    f = np.asarray(t, dtype=np.float64).reshape(-1)
+    return f if f.size <= 4096 else f[::SAMPLE_STRIDE]
+
+
+def state_digest(sd):
+    """Per key (sum, sum of |v|, sum of v * (1 + index mod 7)) in float64: pins a seeded initial state_dict."""
+    d = {}
+    for k, v in sd.items():
+        f = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)
+        w = 1.0 + (np.arange(f.size) % 7)
+        d[k] = np.array([f.sum(), np.abs(f).sum(), (f * w).sum(), f.size], dtype=np.float64)
+    return d
+
+
+DIGEST_MODELS = ((10, 40, 101), (35, 13, 32))   # (classes, time_len, seq_len) whose seeded init is pinned
+DIGEST_SEED = 1234
