@@ -32,6 +32,40 @@ CASES = {
     "long": (5, 101, 40, 10, 14),          # odd T, the longest recurrence
 }
 
+# The accepted shape range of abd_lstmattn_create (T in [1, 1024], F in [1, 128], K in [1, 4096]) beyond CASES:
+# the smallest shapes that reach each loop bound and cap of csrc/lstm_attn.hip.  Same form and the same seed
+# conditions (tests/test_lstm_attention_cpu.py); these are compared with the restatement only, which CASES
+# pin to the reference module and which is parametric in T, F and K.
+ENVELOPE = {
+    "below_conv": (2, 1, 3, 10, 31),       # T = 1: dW_hh memset, every outer conv tap off, dav[0] alone
+    "short_seq": (3, 3, 5, 10, 32),        # T < 5: partial conv taps on both sides
+    "wide_classes": (3, 7, 13, 200, 321),  # K > 128: second trip of the head's logits loop, 4 trips in ce_kernel
+    "one_class": (3, 7, 13, 1, 34),        # K = 1: loss 0, every gradient 0
+    "strided_head": (2, 257, 5, 10, 45),   # T = 2 * 128 + 1: three trips of head_bwd's dav loop
+    "cap_seq": (1, 1024, 1, 10, 36),       # T at the cap, F = 1, one row
+    "wide_feature": (2, 9, 128, 10, 37),   # F at the cap
+    "ragged_feature": (TILE + 1, 6, 33, 70, 38),   # F one past a GEMM tile, K in (64, 128], a ragged batch tile
+    "big_batch": (600, 28, 16, 10, 178),   # B > 512: ksplit 64 with kchunk 264 (no multiple of 28), 128 slabs,
+                                           # two-stage column sums, a third trip of metrics_kernel
+}
+
+# (case, gradient tensor) -> bound of the device result, where float32 on the CPU misses 1e-5: ten times the
+# float32-CPU distance measured for that seed (the margin the 1e-4 / 1e-5 pair keeps).  Everything else: 1e-4.
+# big_batch conv1.bias: a cancelling sum over 268800 elements; float32 on the CPU is 1.2e-5 .. 1.8e-5 from float64
+# depending on torch's thread count (1 .. 32 tried), no seed of 200 tried brought every conv tensor under 1e-5
+# with the logit gap kept.  The device accumulates these sums in double.
+ENVELOPE_BOUNDS = {("big_batch", "conv1.bias"): 1.8e-4}
+
+
+def geometry(name):
+    """(B, T, F, K, seed) of a case of either table."""
+    return CASES[name] if name in CASES else ENVELOPE[name]
+
+
+def grad_bound(name, tensor, default=1e-4):
+    return ENVELOPE_BOUNDS.get((name, tensor), default)
+
+
 _RNN = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
         "weight_ih_l0_reverse", "weight_hh_l0_reverse", "bias_ih_l0_reverse", "bias_hh_l0_reverse")
 PARAM_ORDER = (
@@ -65,7 +99,7 @@ def param_shapes(T, Fd, K):
 
 def make_state(name):
     """The case's state_dict as numpy arrays (float32 parameters / statistics, int64 counters)."""
-    B, T, Fd, K, seed = CASES[name]
+    B, T, Fd, K, seed = geometry(name)
     r = np.random.Generator(np.random.PCG64(1000 + seed))
     st = {}
     for n, shp in param_shapes(T, Fd, K).items():
@@ -93,7 +127,7 @@ def make_state(name):
 
 def make_inputs(name):
     """x (B,1,T,F) float32, labels, indicators (int64), dropout keep-mask (B,64) uint8."""
-    B, T, Fd, K, seed = CASES[name]
+    B, T, Fd, K, seed = geometry(name)
     r = np.random.Generator(np.random.PCG64(2000 + seed))
     x = (20.0 * r.normal(size=(B, 1, T, Fd))).astype(np.float32)
     y = r.integers(0, K, B).astype(np.int64)

@@ -33,7 +33,7 @@ def dev():
 
 
 def build(name, dev):
-    B, Tn, Fd, K, _ = lc.CASES[name]
+    B, Tn, Fd, K, _ = lc.geometry(name)
     m = lstmwithattention(K, Fd, Tn)
     m.load_state_dict({k: torch.tensor(v) for k, v in lc.make_state(name).items()})
     return m.to(dev)
@@ -137,7 +137,7 @@ def test_gradients_and_saved_states(dev, name):
 def _autograd_and_step(dev, name):
     """Gradients of the autograd path (abd_lstmattn_forward, torch's CrossEntropyLoss, abd_lstmattn_backward)
     and of the fused step under the same CPU-drawn mask, with the restatement's for that mask."""
-    B, Tn, Fd, K, _ = lc.CASES[name]
+    B, Tn, Fd, K, _ = lc.geometry(name)
     x, y, ind, _ = inputs(name, dev)
     m2 = build(name, dev).train()
     m2.set_dropout_source("torch_cpu")

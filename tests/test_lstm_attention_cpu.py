@@ -56,6 +56,28 @@ def test_fixture_float32_margin_and_logit_gaps(name):
     assert lc.rel_err(torch.cat([a["h1"][0], a["h1"][1]], -1), a["y1"]) < 1e-12
 
 
+@pytest.mark.parametrize("name", list(lc.ENVELOPE))
+def test_envelope_float32_margin_and_logit_gaps(name):
+    """The same conditions for the accepted-shape-range cases (lc.ENVELOPE), which the GPU bounds of
+    tests/test_gpu_lstm_envelope.py rest on: float32 logits within 1e-5 of float64, the top-2 gap above 1e-3
+    (one_class has one logit), every gradient tensor within 1e-5 -- or, where lc.ENVELOPE_BOUNDS records a
+    measured device bound, within a tenth of it."""
+    B, Tn, Fd, K, _ = lc.ENVELOPE[name]
+    a, b = lc.run_case(name, torch.float64), lc.run_case(name, torch.float32)
+    assert a["eval_logits"].shape == (B, K) and a["y2"].shape == (B, Tn, 128)
+    for k in ("eval_logits", "train_logits"):
+        assert lc.rel_err(b[k], a[k]) < 1e-5, k
+        if K > 1:
+            top = a[k].topk(2, dim=1).values
+            assert float(((top[:, 0] - top[:, 1]) / a[k].abs().max()).min()) > 1e-3, k
+    for n in lc.PARAM_ORDER:
+        assert lc.rel_err(b["grads"][n], a["grads"][n]) < 0.1 * lc.grad_bound(name, n), n
+    if name == "one_class":
+        assert float(a["loss"]) == 0.0 and all(float(g.abs().max()) == 0.0 for g in a["grads"].values())
+    assert lc.rel_err(torch.cat([a["h2"][0], a["h2"][1]], -1), a["y2"]) < 1e-12
+    assert lc.rel_err(torch.cat([a["h1"][0], a["h1"][1]], -1), a["y1"]) < 1e-12
+
+
 @pytest.mark.parametrize("geo", lc.DIGEST_MODELS)
 def test_seeded_init_and_state_dict_match_the_reference(geo):
     K, Fd, Tn = geo
@@ -145,6 +167,12 @@ def test_create_refuses_unsupported_geometry():
     assert lib.abd_lstmattn_create(32, 129, 10, C.byref(h)) == 1002
     assert lib.abd_lstmattn_create(0, 13, 10, C.byref(h)) == 1002
     assert lib.abd_lstmattn_create(1025, 13, 10, C.byref(h)) == 1002
+    assert lib.abd_lstmattn_create(32, 0, 10, C.byref(h)) == 1002
+    assert lib.abd_lstmattn_create(32, 13, 0, C.byref(h)) == 1002
+    assert lib.abd_lstmattn_create(32, 13, 4097, C.byref(h)) == 1002
+    for geo in ((1, 13, 10), (1024, 13, 10), (32, 1, 10), (32, 128, 10), (32, 13, 1), (32, 13, 4096)):   # the limits
+        assert lib.abd_lstmattn_create(*geo, C.byref(h)) == 0, geo
+        lib.abd_lstmattn_destroy(h)
     assert lib.abd_lstmattn_create(101, 40, 10, C.byref(h)) == 0
     offs = (C.c_int64 * 35)()
     assert lib.abd_lstmattn_param_offsets(h, offs) == 0
