@@ -39,6 +39,9 @@ EXPORTS = (
     "abd_lstmattn_create", "abd_lstmattn_destroy", "abd_lstmattn_param_count", "abd_lstmattn_param_offsets",
     "abd_lstmattn_tile_rows", "abd_lstmattn_workspace_bytes", "abd_lstmattn_workspace_offset", "abd_lstmattn_forward",
     "abd_lstmattn_backward", "abd_lstmattn_train_step", "abd_lstmattn_eval",
+    "abd_rnn_create", "abd_rnn_destroy", "abd_rnn_param_count", "abd_rnn_param_offsets", "abd_rnn_tile_info",
+    "abd_rnn_workspace_bytes", "abd_rnn_workspace_offset", "abd_rnn_forward", "abd_rnn_backward",
+    "abd_rnn_train_step", "abd_rnn_eval",
     "abd_profile_start", "abd_profile_start_every", "abd_profile_step", "abd_profile_stop",
 )
 
@@ -105,6 +108,18 @@ class LstmAttnArgs(C.Structure):
         ("mask_out", C.c_void_p), ("logits_out", C.c_void_p),
         ("metrics", C.c_void_p), ("grad_scale", C.c_float), ("num_batches_tracked", C.c_void_p),
         ("row_offset", C.c_int64),
+    ]
+
+
+class RnnArgs(C.Structure):
+    """abd_rnn_args: abd_lstmattn_args without the dropout and running-statistics fields."""
+    _fields_ = [
+        ("x", C.c_void_p), ("labels", C.c_void_p), ("indicators", C.c_void_p), ("batch", C.c_int64),
+        ("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("adam_step", C.c_int64),
+        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("do_update", C.c_int),
+        ("logits_out", C.c_void_p), ("metrics", C.c_void_p), ("grad_scale", C.c_float),
     ]
 
 
@@ -262,6 +277,17 @@ def _declare(lib):
         "abd_lstmattn_backward": (i32, [vp, C.POINTER(LstmAttnArgs), vp, vp, sz, vp]),
         "abd_lstmattn_train_step": (i32, [vp, C.POINTER(LstmAttnArgs), vp, sz, vp]),
         "abd_lstmattn_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "abd_rnn_create": (i32, [i32, i32, i32, C.POINTER(vp)]),
+        "abd_rnn_destroy": (None, [vp]),
+        "abd_rnn_param_count": (i64, [vp]),
+        "abd_rnn_param_offsets": (i32, [vp, C.POINTER(i64)]),
+        "abd_rnn_tile_info": (i32, [i32]),
+        "abd_rnn_workspace_bytes": (sz, [vp, i64]),
+        "abd_rnn_workspace_offset": (i64, [vp, i64, C.c_char_p]),
+        "abd_rnn_forward": (i32, [vp, C.POINTER(RnnArgs), vp, sz, vp]),
+        "abd_rnn_backward": (i32, [vp, C.POINTER(RnnArgs), vp, vp, sz, vp]),
+        "abd_rnn_train_step": (i32, [vp, C.POINTER(RnnArgs), vp, sz, vp]),
+        "abd_rnn_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
         "abd_profile_start": (i32, [C.c_ulonglong, i32]),
         "abd_profile_start_every": (i32, [C.c_ulonglong, i32, i32]),
         "abd_profile_step": (i32, []),

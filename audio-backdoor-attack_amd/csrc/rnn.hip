@@ -1,0 +1,680 @@
+// RNN (reference utils/models.py:231-257) on gfx950: nn.LSTM(F, 768, 3, batch_first) -> nn.Linear(768, K)
+// on the last time step, cross entropy, BPTT.  Every product is fp32 (v_mfma_f32_32x32x2_f32).
+//
+// GEMMs: gemm_tiled_kernel, an LDS-tiled block of 4 waves (2 x 2), each wave TM x TN accumulator tiles
+// of 32 x 32; the block tile is (64 TM) x (64 TN) x 32.  Both operands are staged through LDS; strides
+// select the NN / NT / TN forms, ragged M / N / K are zero-filled on load and masked on store.  A long
+// reduction (the weight gradients' B*T rows) is split over blockIdx.z into slices whose partial products
+// colsum_kernel sums in slice order: no float atomics, two runs are bit-equal.
+//
+// Recurrence: one launch per time step and layer, the kernel boundary being the only synchronisation
+// between steps.  One layer's W_hh is 4*768*768*4 B = 9.4 MB, so it cannot stay in LDS as lstm_attn.hip's
+// 64 KiB one does; each step streams it (from L2 / MALL) through LDS.  rnn_step_fwd_kernel: a workgroup
+// owns kRecRows batch rows and 32 hidden units; wave g accumulates gate g of those units, so the
+// workgroup holds i, f, g and o of its units and finishes c_t and h_t in its epilogue.
+#include <algorithm>
+#include <cmath>
+
+#include "abd_common.h"
+
+struct abd_rnn {
+  int T, F, K;
+  int64_t off[15];
+};
+
+namespace {
+
+constexpr int kT = 256;
+constexpr int kHid = 768;          // LSTM hidden size
+constexpr int kGates = 4 * kHid;   // gate rows, torch order i f g o
+constexpr int kLayers = 3;
+constexpr int kBK = 32;            // K-step of the tiled kernels
+constexpr int kRecRows = 32;       // batch rows of one recurrent workgroup
+constexpr int kRecUnits = 32;      // hidden units of one recurrent workgroup
+constexpr int kSmallTile = 64, kLargeTile = 128;
+constexpr int kLargeMinBlocks = 96;  // below this many 128 x 128 blocks the 64 x 64 tile fills more CUs
+constexpr int kSliceRows = 256;    // least rows of one weight-gradient slice
+constexpr int kMaxSlices = 8;
+constexpr int kColsumRows = 512;   // above this many rows the column sums run in two stages
+
+enum { P_FCW = 4 * kLayers, P_FCB, P_COUNT };
+
+#include "reduce_ce.inc"
+
+__device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+typedef float f16v __attribute__((ext_vector_type(16)));
+
+// ------------------------------------------------------------------ LDS-tiled fp32 MFMA GEMM
+// C[m][n] (+)= sum_k A(m,k) B(k,n) (+ bias1[n] + bias2[n]); A(m,k) = A[m*sam + k*sak],
+// B(k,n) = B[kb*sbk + n*sbn].  shift != 0: kb = k + shift when k's step (k % T) + shift stays inside
+// [0, T), else the term is zero (h_{t-1} of the recurrent weight gradient).  blockIdx.z takes the
+// k-slice [z*kchunk, (z+1)*kchunk) and writes C + z*cz.
+struct GemmArgs {
+  const float* A;
+  const float* B;
+  float* C;
+  int M, N, K;
+  int64_t sam, sak, sbk, sbn, ldc, cz;
+  const float* bias1;
+  const float* bias2;
+  int accumulate, kchunk, T, shift;
+};
+
+// An operand tile in LDS: [row][kBK + 1] when k is the contiguous index in memory, [k][rows + 32] when
+// the row is.  Either way consecutive threads write consecutive words, and the MFMA's operand read
+// (lanes 0..31: 32 rows at k, lanes 32..63: the same rows at k + 1) touches 64 different banks.
+template <int TM, int TN>
+__global__ void __launch_bounds__(kT) gemm_tiled_kernel(GemmArgs a) {
+  constexpr int BM = 64 * TM, BN = 64 * TN;
+  constexpr int NA = BM * kBK / kT, NB = BN * kBK / kT;
+  __shared__ float As[kBK * (BM + 32)];
+  __shared__ float Bs[kBK * (BN + 32)];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wm = (w >> 1) * TM * 32, wn = (w & 1) * TN * 32;
+  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+  const int k0 = blockIdx.z * a.kchunk;
+  const int k1 = min(a.K, k0 + a.kchunk);
+  const bool a_kc = a.sak == 1, b_kc = a.sbk == 1;
+  const int a_sm = a_kc ? kBK + 1 : 1, a_sk = a_kc ? 1 : BM + 32;
+  const int b_sn = b_kc ? kBK + 1 : 1, b_sk = b_kc ? 1 : BN + 32;
+  f16v acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  for (int kb = k0; kb < k1; kb += kBK) {
+    float ar[NA], br[NB];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int e = tid + i * kT;
+      const int m = a_kc ? e >> 5 : e % BM, k = a_kc ? e & 31 : e / BM;
+      const int gm = m0 + m, gk = kb + k;
+      ar[i] = (gm < a.M && gk < k1) ? a.A[(int64_t)gm * a.sam + (int64_t)gk * a.sak] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int e = tid + i * kT;
+      const int n = b_kc ? e >> 5 : e % BN, k = b_kc ? e & 31 : e / BN;
+      const int gn = n0 + n, gk = kb + k;
+      float v = 0.0f;
+      if (gn < a.N && gk < k1) {
+        if (a.shift == 0) {
+          v = a.B[(int64_t)gk * a.sbk + (int64_t)gn * a.sbn];
+        } else {
+          const int ts = gk % a.T + a.shift;
+          if (ts >= 0 && ts < a.T) v = a.B[(int64_t)(gk + a.shift) * a.sbk + (int64_t)gn * a.sbn];
+        }
+      }
+      br[i] = v;
+    }
+    __syncthreads();   // the previous tile's operand reads are done
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int e = tid + i * kT;
+      const int m = a_kc ? e >> 5 : e % BM, k = a_kc ? e & 31 : e / BM;
+      As[m * a_sm + k * a_sk] = ar[i];
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int e = tid + i * kT;
+      const int n = b_kc ? e >> 5 : e % BN, k = b_kc ? e & 31 : e / BN;
+      Bs[n * b_sn + k * b_sk] = br[i];
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int kk = 0; kk < kBK / 2; ++kk) {
+      const int k = 2 * kk + (lane >> 5);
+      float av[TM], bv[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) av[i] = As[(wm + i * 32 + (lane & 31)) * a_sm + k * a_sk];
+#pragma unroll
+      for (int j = 0; j < TN; ++j) bv[j] = Bs[(wn + j * 32 + (lane & 31)) * b_sn + k * b_sk];
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+    }
+  }
+  float* C = a.C + (int64_t)blockIdx.z * a.cz;
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int n = n0 + wn + j * 32 + (lane & 31);
+    if (n >= a.N) continue;
+    float bias = 0.0f;
+    if (a.bias1) bias += a.bias1[n];
+    if (a.bias2) bias += a.bias2[n];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (m < a.M) {
+          float* c = C + (int64_t)m * a.ldc + n;
+          const float v = acc[i][j][r] + bias;
+          *c = a.accumulate ? *c + v : v;
+        }
+      }
+  }
+}
+
+// ------------------------------------------------------------------ recurrence
+struct StepArgs {
+  float* gates;        // [B*T][3072]: x_t W_ih^T + b_ih + b_hh on entry, activated i f g o on exit
+  float* h;            // [B][T][768]
+  float* c;            // [B][T][768]
+  const float* whh;    // [3072][768]
+  const float* dy;     // backward: [B][T][768] gradient of this layer's output, or NULL
+  const float* dhrec;  // backward: [B][768] dG_{t+1} W_hh (the head's dh at the top layer's last step), or NULL
+  float* dc;           // backward: [B][768] carried cell gradient
+  int B, T, t;
+};
+
+// step t of one layer: G_t = XP_t + h_{t-1} W_hh^T, activations, c_t, h_t.  grid (ceil(B / 32), 24).
+__global__ void __launch_bounds__(kT) rnn_step_fwd_kernel(StepArgs a) {
+  __shared__ float Hs[kRecRows * (kBK + 1)];
+  __shared__ float Ws[4 * kRecUnits * (kBK + 1)];
+  __shared__ float Es[4][kRecRows][kRecUnits + 1];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b0 = blockIdx.x * kRecRows, u0 = blockIdx.y * kRecUnits;
+  const int T = a.T, t = a.t;
+  f16v acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  if (t > 0) {   // h_{-1} = 0: nothing to multiply at the first step
+    for (int kb = 0; kb < kHid; kb += kBK) {
+      float hr[kRecRows * kBK / kT], wr[4 * kRecUnits * kBK / kT];
+#pragma unroll
+      for (int i = 0; i < kRecRows * kBK / kT; ++i) {
+        const int e = tid + i * kT, k = e & 31, m = e >> 5, b = b0 + m;
+        hr[i] = b < a.B ? a.h[((int64_t)b * T + t - 1) * kHid + kb + k] : 0.0f;
+      }
+#pragma unroll
+      for (int i = 0; i < 4 * kRecUnits * kBK / kT; ++i) {
+        const int e = tid + i * kT, k = e & 31, j = e >> 5;   // j = gate * 32 + unit
+        wr[i] = a.whh[((int64_t)(j >> 5) * kHid + u0 + (j & 31)) * kHid + kb + k];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < kRecRows * kBK / kT; ++i) {
+        const int e = tid + i * kT;
+        Hs[(e >> 5) * (kBK + 1) + (e & 31)] = hr[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 4 * kRecUnits * kBK / kT; ++i) {
+        const int e = tid + i * kT;
+        Ws[(e >> 5) * (kBK + 1) + (e & 31)] = wr[i];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int kk = 0; kk < kBK / 2; ++kk) {
+        const int k = 2 * kk + (lane >> 5);
+        const float av = Hs[(lane & 31) * (kBK + 1) + k];
+        const float bv = Ws[(w * kRecUnits + (lane & 31)) * (kBK + 1) + k];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) Es[w][(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)][lane & 31] = acc[r];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kRecRows * kRecUnits / kT; ++i) {
+    const int e = tid + i * kT, u = e & 31, m = e >> 5, b = b0 + m;
+    if (b >= a.B) continue;
+    const int64_t row = (int64_t)b * T + t;
+    float* gp = a.gates + row * kGates + u0 + u;
+    const float ig = sigmoid_acc(gp[0] + Es[0][m][u]);
+    const float fg = sigmoid_acc(gp[kHid] + Es[1][m][u]);
+    const float gg = tanhf(gp[2 * kHid] + Es[2][m][u]);
+    const float og = sigmoid_acc(gp[3 * kHid] + Es[3][m][u]);
+    const float cp = t > 0 ? a.c[(row - 1) * kHid + u0 + u] : 0.0f;
+    const float ct = fg * cp + ig * gg;
+    gp[0] = ig;
+    gp[kHid] = fg;
+    gp[2 * kHid] = gg;
+    gp[3 * kHid] = og;
+    a.c[row * kHid + u0 + u] = ct;
+    a.h[row * kHid + u0 + u] = og * tanhf(ct);
+  }
+}
+
+// step t of one layer's BPTT: the pre-activation gate gradients dG_t, written over the activated gates of
+// that step (nothing reads them again), and the carried cell gradient.  One thread per (row, unit).
+__global__ void __launch_bounds__(kT) rnn_gate_bwd_kernel(StepArgs a) {
+  const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (e >= (int64_t)a.B * kHid) return;
+  const int b = (int)(e / kHid), u = (int)(e - (int64_t)b * kHid);
+  const int T = a.T, t = a.t;
+  const int64_t row = (int64_t)b * T + t;
+  float* gp = a.gates + row * kGates + u;
+  const float ig = gp[0], fg = gp[kHid], gg = gp[2 * kHid], og = gp[3 * kHid];
+  const float ct = a.c[row * kHid + u];
+  const float cp = t > 0 ? a.c[(row - 1) * kHid + u] : 0.0f;
+  float dht = a.dy ? a.dy[row * kHid + u] : 0.0f;
+  if (a.dhrec) dht += a.dhrec[e];
+  const float dcin = t < T - 1 ? a.dc[e] : 0.0f;
+  const float tc = tanhf(ct);
+  const float dct = dcin + dht * og * (1.0f - tc * tc);
+  gp[0] = dct * gg * ig * (1.0f - ig);
+  gp[kHid] = dct * cp * fg * (1.0f - fg);
+  gp[2 * kHid] = dct * ig * (1.0f - gg * gg);
+  gp[3 * kHid] = dht * tc * og * (1.0f - og);
+  a.dc[e] = dct * fg;
+}
+
+// ------------------------------------------------------------------ host side
+// workspace map (byte offsets); every buffer 256-byte aligned
+struct Layout {
+  size_t h[kLayers], c[kLayers], gates[kLayers], dy, dhtop, dhrec, dc, logits, dlogits, rowinfo, slab, colp, total;
+  int ksplit;
+  int64_t kchunk;
+};
+
+Layout make_layout(const abd_rnn* n, int64_t B) {
+  Layout L{};
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t r = o;
+    o += (bytes + 255) & ~(size_t)255;
+    return r;
+  };
+  const size_t BT = (size_t)B * n->T;
+  for (int l = 0; l < kLayers; ++l) {
+    L.h[l] = take(4 * BT * kHid);
+    L.c[l] = take(4 * BT * kHid);
+    L.gates[l] = take(4 * BT * kGates);   // input projections, activated gates, then gate gradients
+  }
+  L.dy = take(4 * BT * kHid);             // gradient of the output of the layer below the one in hand
+  L.dhtop = take(4 * (size_t)B * kHid);
+  L.dhrec = take(4 * (size_t)B * kHid);
+  L.dc = take(4 * (size_t)B * kHid);
+  L.logits = take(4 * (size_t)B * n->K);
+  L.dlogits = take(4 * (size_t)B * n->K);
+  L.rowinfo = take(4 * (size_t)B * 4);
+  // weight-gradient GEMMs: B*T rows of reduction split into slices of >= kSliceRows rows
+  L.ksplit = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxSlices, (int64_t)BT / kSliceRows));
+  L.kchunk = ((int64_t)BT + L.ksplit - 1) / L.ksplit;
+  L.kchunk = (L.kchunk + kBK - 1) / kBK * kBK;
+  L.ksplit = (int)(((int64_t)BT + L.kchunk - 1) / L.kchunk);
+  L.slab = take(L.ksplit > 1 ? 4 * (size_t)L.ksplit * kGates * kHid : 0);
+  L.colp = take(4 * (size_t)64 * kGates);
+  L.total = o;
+  return L;
+}
+
+struct Ctx {
+  const abd_rnn* n;
+  Layout L;
+  char* ws;
+  hipStream_t s;
+  int64_t B;
+  const float* params;
+  float* grads;
+  template <class Tp> Tp* at(size_t off) const { return reinterpret_cast<Tp*>(ws + off); }
+  const float* p(int i) const { return params + n->off[i]; }
+  float* g(int i) const { return grads + n->off[i]; }
+};
+
+int launch_gemm(hipStream_t s, GemmArgs g, int ksplit = 1) {
+  if (g.M <= 0 || g.N <= 0) return ABD_OK;
+  ksplit = std::max(1, ksplit);
+  if (ksplit == 1) g.kchunk = std::max(g.K, 1);
+  const int64_t large = (int64_t)((g.M + kLargeTile - 1) / kLargeTile) * ((g.N + kLargeTile - 1) / kLargeTile) * ksplit;
+  if (large >= kLargeMinBlocks) {
+    dim3 grid((g.M + kLargeTile - 1) / kLargeTile, (g.N + kLargeTile - 1) / kLargeTile, ksplit);
+    gemm_tiled_kernel<2, 2><<<grid, kT, 0, s>>>(g);
+  } else {
+    dim3 grid((g.M + kSmallTile - 1) / kSmallTile, (g.N + kSmallTile - 1) / kSmallTile, ksplit);
+    gemm_tiled_kernel<1, 1><<<grid, kT, 0, s>>>(g);
+  }
+  ABD_LAUNCH_CHECK();
+  return ABD_OK;
+}
+
+// out[cols] = column sums of A (rows x cols, leading dimension ld); two fixed-order stages past kColsumRows
+int launch_colsum(const Ctx& c, const float* A, int64_t rows, int64_t cols, int64_t ld, float* out) {
+  const int nb = (int)((cols + kRedT - 1) / kRedT);
+  const int S = (cols <= kGates && rows > kColsumRows) ? (int)std::min<int64_t>(64, rows / 256) : 1;
+  if (S <= 1) {
+    colsum_kernel<<<dim3(nb, 1), kRedT, 0, c.s>>>(A, rows, cols, ld, rows, out, 0, 0);
+    ABD_LAUNCH_CHECK();
+    return ABD_OK;
+  }
+  const int64_t chunk = (rows + S - 1) / S;
+  float* part = c.at<float>(c.L.colp);
+  colsum_kernel<<<dim3(nb, S), kRedT, 0, c.s>>>(A, rows, cols, ld, chunk, part, cols, 0);
+  ABD_LAUNCH_CHECK();
+  colsum_kernel<<<dim3(nb, 1), kRedT, 0, c.s>>>(part, S, cols, cols, S, out, 0, 0);
+  ABD_LAUNCH_CHECK();
+  return ABD_OK;
+}
+
+// dW[j][i] = sum_rows dg[row][j] act[row][i] over all B*T rows, sliced (shift -1: act one step back)
+int weight_grad(const Ctx& c, const float* dg, const float* act, int in, int shift, float* out) {
+  const int64_t BT = c.B * c.n->T;
+  GemmArgs g{};
+  g.A = dg;
+  g.B = act;
+  g.M = kGates;
+  g.N = in;
+  g.K = (int)BT;
+  g.sam = 1;
+  g.sak = kGates;
+  g.sbk = in;
+  g.sbn = 1;
+  g.ldc = in;
+  g.T = c.n->T;
+  g.shift = shift;
+  if (c.L.ksplit <= 1) {
+    g.C = out;
+    return launch_gemm(c.s, g);
+  }
+  g.C = c.at<float>(c.L.slab);
+  g.cz = (int64_t)kGates * in;
+  g.kchunk = (int)c.L.kchunk;
+  if (int rc = launch_gemm(c.s, g, c.L.ksplit)) return rc;
+  return launch_colsum(c, g.C, c.L.ksplit, g.cz, g.cz, out);
+}
+
+int run_forward(const Ctx& c, const float* x) {
+  const int T = c.n->T;
+  const int64_t BT = c.B * T;
+  const float* in = x;
+  int width = c.n->F;
+  for (int l = 0; l < kLayers; ++l) {
+    float* gates = c.at<float>(c.L.gates[l]);
+    GemmArgs g{};   // x W_ih^T + b_ih + b_hh over all B*T rows
+    g.A = in;
+    g.B = c.p(4 * l);
+    g.C = gates;
+    g.M = (int)BT;
+    g.N = kGates;
+    g.K = width;
+    g.sam = width;
+    g.sak = 1;
+    g.sbk = 1;
+    g.sbn = width;
+    g.ldc = kGates;
+    g.bias1 = c.p(4 * l + 2);
+    g.bias2 = c.p(4 * l + 3);
+    if (int rc = launch_gemm(c.s, g)) return rc;
+    StepArgs sa{};
+    sa.gates = gates;
+    sa.h = c.at<float>(c.L.h[l]);
+    sa.c = c.at<float>(c.L.c[l]);
+    sa.whh = c.p(4 * l + 1);
+    sa.B = (int)c.B;
+    sa.T = T;
+    const dim3 grid((unsigned)((c.B + kRecRows - 1) / kRecRows), kHid / kRecUnits);
+    for (int t = 0; t < T; ++t) {
+      sa.t = t;
+      rnn_step_fwd_kernel<<<grid, kT, 0, c.s>>>(sa);
+      ABD_LAUNCH_CHECK();
+    }
+    in = sa.h;
+    width = kHid;
+  }
+  GemmArgs f{};   // fc on the top layer's last step
+  f.A = c.at<float>(c.L.h[kLayers - 1]) + (int64_t)(T - 1) * kHid;
+  f.B = c.p(P_FCW);
+  f.C = c.at<float>(c.L.logits);
+  f.M = (int)c.B;
+  f.N = c.n->K;
+  f.K = kHid;
+  f.sam = (int64_t)T * kHid;
+  f.sak = 1;
+  f.sbk = 1;
+  f.sbn = kHid;
+  f.ldc = c.n->K;
+  f.bias1 = c.p(P_FCB);
+  return launch_gemm(c.s, f);
+}
+
+int run_ce(const Ctx& c, const int64_t* labels, const int64_t* ind, bool grad, float grad_scale, float* logits_out,
+           int64_t* metrics) {
+  CeArgs ce{};
+  ce.logits = c.at<float>(c.L.logits);
+  ce.labels = labels;
+  ce.ind = ind;
+  ce.dlogits = grad ? c.at<float>(c.L.dlogits) : nullptr;
+  ce.rowinfo = c.at<float>(c.L.rowinfo);
+  ce.logits_out = logits_out;
+  ce.K = c.n->K;
+  ce.scale = grad_scale / (float)c.B;
+  if (!labels && !logits_out) return ABD_OK;
+  ce_kernel<<<(unsigned)c.B, 64, 0, c.s>>>(ce);
+  ABD_LAUNCH_CHECK();
+  if (labels && metrics) {
+    metrics_kernel<<<1, kRedT, 0, c.s>>>(ce.rowinfo, (int)c.B, metrics, (double)grad_scale);
+    ABD_LAUNCH_CHECK();
+  }
+  return ABD_OK;
+}
+
+int run_backward(const Ctx& c, const float* x, const float* dlogits) {
+  const int T = c.n->T, K = c.n->K;
+  const int64_t BT = c.B * T;
+  const float* hlast = c.at<float>(c.L.h[kLayers - 1]) + (int64_t)(T - 1) * kHid;
+  {
+    GemmArgs g{};   // dfc.weight[j][i] = sum_b dlogits[b][j] h_{T-1}[b][i]
+    g.A = dlogits;
+    g.B = hlast;
+    g.C = c.g(P_FCW);
+    g.M = K;
+    g.N = kHid;
+    g.K = (int)c.B;
+    g.sam = 1;
+    g.sak = K;
+    g.sbk = (int64_t)T * kHid;
+    g.sbn = 1;
+    g.ldc = kHid;
+    if (int rc = launch_gemm(c.s, g)) return rc;
+    if (int rc = launch_colsum(c, dlogits, c.B, K, K, c.g(P_FCB))) return rc;
+    GemmArgs d{};   // dh_{T-1} of the top layer = dlogits fc.weight; its dy is zero everywhere else
+    d.A = dlogits;
+    d.B = c.p(P_FCW);
+    d.C = c.at<float>(c.L.dhtop);
+    d.M = (int)c.B;
+    d.N = kHid;
+    d.K = K;
+    d.sam = K;
+    d.sak = 1;
+    d.sbk = kHid;
+    d.sbn = 1;
+    d.ldc = kHid;
+    if (int rc = launch_gemm(c.s, d)) return rc;
+  }
+  float* dy = c.at<float>(c.L.dy);
+  float* dhrec = c.at<float>(c.L.dhrec);
+  for (int l = kLayers - 1; l >= 0; --l) {
+    const bool top = l == kLayers - 1;
+    float* gates = c.at<float>(c.L.gates[l]);
+    const float* h = c.at<float>(c.L.h[l]);
+    const float* in = l ? c.at<float>(c.L.h[l - 1]) : x;
+    const int width = l ? kHid : c.n->F;
+    StepArgs sa{};
+    sa.gates = gates;
+    sa.c = c.at<float>(c.L.c[l]);
+    sa.dy = top ? nullptr : dy;
+    sa.dc = c.at<float>(c.L.dc);
+    sa.B = (int)c.B;
+    sa.T = T;
+    GemmArgs r{};   // dh_{t-1} = dG_t W_hh
+    r.B = c.p(4 * l + 1);
+    r.C = dhrec;
+    r.M = (int)c.B;
+    r.N = kHid;
+    r.K = kGates;
+    r.sam = (int64_t)T * kGates;
+    r.sak = 1;
+    r.sbk = kHid;
+    r.sbn = 1;
+    r.ldc = kHid;
+    const unsigned nblk = (unsigned)((c.B * kHid + kT - 1) / kT);
+    for (int t = T - 1; t >= 0; --t) {
+      sa.t = t;
+      sa.dhrec = t == T - 1 ? (top ? c.at<float>(c.L.dhtop) : nullptr) : dhrec;
+      rnn_gate_bwd_kernel<<<nblk, kT, 0, c.s>>>(sa);
+      ABD_LAUNCH_CHECK();
+      if (t > 0) {
+        r.A = gates + (int64_t)t * kGates;
+        if (int rc = launch_gemm(c.s, r)) return rc;
+      }
+    }
+    if (int rc = weight_grad(c, gates, in, width, 0, c.g(4 * l))) return rc;
+    if (T > 1) {
+      if (int rc = weight_grad(c, gates, h, kHid, -1, c.g(4 * l + 1))) return rc;
+    } else {
+      ABD_HIP(hipMemsetAsync(c.g(4 * l + 1), 0, sizeof(float) * kGates * kHid, c.s));
+    }
+    if (int rc = launch_colsum(c, gates, BT, kGates, kGates, c.g(4 * l + 2))) return rc;
+    ABD_HIP(hipMemcpyAsync(c.g(4 * l + 3), c.g(4 * l + 2), sizeof(float) * kGates, hipMemcpyDeviceToDevice, c.s));
+    if (l > 0) {
+      GemmArgs d{};   // gradient of the layer below's output: dG W_ih
+      d.A = gates;
+      d.B = c.p(4 * l);
+      d.C = dy;
+      d.M = (int)BT;
+      d.N = kHid;
+      d.K = kGates;
+      d.sam = kGates;
+      d.sak = 1;
+      d.sbk = kHid;
+      d.sbn = 1;
+      d.ldc = kHid;
+      if (int rc = launch_gemm(c.s, d)) return rc;
+    }
+  }
+  return ABD_OK;
+}
+
+int make_ctx(const abd_rnn* net, int64_t B, const float* params, float* grads, void* ws, size_t bytes,
+             abd_stream_t stream, Ctx* c) {
+  ABD_CHECK(net != nullptr, ABD_E_INVALID, "NULL network");
+  ABD_CHECK(B >= 1 && B * (int64_t)net->T * kGates < (1LL << 31), ABD_E_INVALID,
+            "batch %lld outside the kernels' 32-bit row range", (long long)B);
+  ABD_CHECK(params != nullptr, ABD_E_INVALID, "NULL params");
+  c->n = net;
+  c->L = make_layout(net, B);
+  ABD_CHECK(ws != nullptr && bytes >= c->L.total, ABD_E_WORKSPACE, "workspace %zu < %zu bytes", bytes, c->L.total);
+  ABD_CHECK((reinterpret_cast<uintptr_t>(ws) & 15) == 0, ABD_E_INVALID, "workspace must be 16-byte aligned");
+  c->ws = static_cast<char*>(ws);
+  c->s = static_cast<hipStream_t>(stream);
+  c->B = B;
+  c->params = params;
+  c->grads = grads;
+  return ABD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int abd_rnn_tile_info(int what) {
+  switch (what) {
+    case 0: return kRecRows;
+    case 1: return kSmallTile;
+    case 2: return kLargeTile;
+    case 3: return kSliceRows;
+    case 4: return kColsumRows;
+    case 5: return kLargeMinBlocks;
+    default: return -1;
+  }
+}
+
+int abd_rnn_create(int T, int F, int num_classes, abd_rnn** net) {
+  ABD_CHECK(net != nullptr, ABD_E_INVALID, "NULL out pointer");
+  ABD_CHECK(F >= 1 && F <= 128, ABD_E_UNSUPPORTED, "RNN: time_len %d outside [1, 128]", F);
+  ABD_CHECK(T >= 1 && T <= 1024, ABD_E_UNSUPPORTED, "RNN: sequence length %d outside [1, 1024]", T);
+  ABD_CHECK(num_classes >= 1 && num_classes <= 4096, ABD_E_UNSUPPORTED, "num_classes must be in [1, 4096]");
+  auto* n = new abd_rnn();
+  n->T = T;
+  n->F = F;
+  n->K = num_classes;
+  n->off[0] = 0;
+  for (int l = 0; l < kLayers; ++l) {
+    const int64_t sz[4] = {(int64_t)kGates * (l ? kHid : F), (int64_t)kGates * kHid, kGates, kGates};
+    for (int i = 0; i < 4; ++i) n->off[4 * l + i + 1] = n->off[4 * l + i] + sz[i];
+  }
+  n->off[P_FCW + 1] = n->off[P_FCW] + (int64_t)num_classes * kHid;
+  n->off[P_FCB + 1] = n->off[P_FCB] + num_classes;
+  *net = n;
+  return ABD_OK;
+}
+
+void abd_rnn_destroy(abd_rnn* net) { delete net; }
+
+int64_t abd_rnn_param_count(const abd_rnn* net) { return net ? net->off[P_COUNT] : 0; }
+
+int abd_rnn_param_offsets(const abd_rnn* net, int64_t* offsets) {
+  ABD_CHECK(net && offsets, ABD_E_INVALID, "NULL argument");
+  for (int i = 0; i <= P_COUNT; ++i) offsets[i] = net->off[i];
+  return ABD_OK;
+}
+
+size_t abd_rnn_workspace_bytes(const abd_rnn* net, int64_t batch) {
+  if (!net || batch < 1) return 0;
+  return make_layout(net, batch).total;
+}
+
+int64_t abd_rnn_workspace_offset(const abd_rnn* net, int64_t batch, const char* name) {
+  if (!net || !name || batch < 1) return -1;
+  const Layout L = make_layout(net, batch);
+  const struct { const char* n; size_t o; } tab[] = {
+      {"h1", L.h[0]}, {"h2", L.h[1]}, {"h3", L.h[2]}, {"c1", L.c[0]}, {"c2", L.c[1]}, {"c3", L.c[2]},
+      {"gates1", L.gates[0]}, {"gates2", L.gates[1]}, {"gates3", L.gates[2]}, {"logits", L.logits},
+      {"dlogits", L.dlogits}, {"rowinfo", L.rowinfo}};
+  for (const auto& e : tab)
+    if (!strcmp(e.n, name)) return (int64_t)e.o;
+  return -1;
+}
+
+int abd_rnn_forward(abd_rnn* net, const abd_rnn_args* a, void* workspace, size_t workspace_bytes,
+                    abd_stream_t stream) {
+  ABD_CHECK(a != nullptr && a->x, ABD_E_INVALID, "NULL x");
+  Ctx c;
+  if (int rc = make_ctx(net, a->batch, a->params, a->grads, workspace, workspace_bytes, stream, &c)) return rc;
+  if (int rc = run_forward(c, a->x)) return rc;
+  return run_ce(c, nullptr, nullptr, false, 1.0f, a->logits_out, nullptr);
+}
+
+int abd_rnn_backward(abd_rnn* net, const abd_rnn_args* a, const float* dlogits, void* workspace,
+                     size_t workspace_bytes, abd_stream_t stream) {
+  ABD_CHECK(a != nullptr && a->x && a->grads && dlogits, ABD_E_INVALID, "NULL x / grads / dlogits");
+  Ctx c;
+  if (int rc = make_ctx(net, a->batch, a->params, a->grads, workspace, workspace_bytes, stream, &c)) return rc;
+  return run_backward(c, a->x, dlogits);
+}
+
+int abd_rnn_train_step(abd_rnn* net, const abd_rnn_args* a, void* workspace, size_t workspace_bytes,
+                       abd_stream_t stream) {
+  ABD_CHECK(a != nullptr && a->x && a->grads, ABD_E_INVALID, "NULL x / grads");
+  ABD_CHECK(a->labels != nullptr, ABD_E_INVALID, "train_step needs labels");
+  ABD_CHECK(!a->do_update || (a->exp_avg && a->exp_avg_sq && a->adam_step >= 1), ABD_E_INVALID,
+            "do_update needs the Adam moments and adam_step >= 1");
+  Ctx c;
+  if (int rc = make_ctx(net, a->batch, a->params, a->grads, workspace, workspace_bytes, stream, &c)) return rc;
+  if (int rc = run_forward(c, a->x)) return rc;
+  if (int rc = run_ce(c, a->labels, a->indicators, true, a->grad_scale, a->logits_out, a->metrics)) return rc;
+  if (int rc = run_backward(c, a->x, c.at<float>(c.L.dlogits))) return rc;
+  if (a->do_update)
+    return abd_adam_f32(a->params, a->grads, a->exp_avg, a->exp_avg_sq, net->off[P_COUNT], a->adam_step, a->lr,
+                        a->beta1, a->beta2, a->eps, stream);
+  return ABD_OK;
+}
+
+int abd_rnn_eval(abd_rnn* net, const float* x, int64_t batch, const float* params, const int64_t* labels,
+                 const int64_t* indicators, float* logits, int64_t* metrics, void* workspace,
+                 size_t workspace_bytes, abd_stream_t stream) {
+  ABD_CHECK(x && logits, ABD_E_INVALID, "NULL x / logits");
+  Ctx c;
+  if (int rc = make_ctx(net, batch, params, nullptr, workspace, workspace_bytes, stream, &c)) return rc;
+  if (int rc = run_forward(c, x)) return rc;
+  return run_ce(c, labels, indicators, false, 1.0f, logits, metrics);
+}
+
+}  // extern "C"

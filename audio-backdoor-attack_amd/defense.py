@@ -98,11 +98,12 @@ def combine(loss_sums, sizes, correct, n: int):
 
 def _refuse_lstm(model, what="the defences"):
     """The defences are smallcnn's (conv1..conv3 / bn1..bn3 / fc1 / fc2 and the abd_smallcnn_* entry points):
-    lstmwithattention, whose engine looks alike but whose flat buffers are laid out differently, is refused;
-    every other module is treated as before."""
+    lstmwithattention and RNN, whose engines look alike but whose flat buffers are laid out differently, are
+    refused; every other module is treated as before."""
     from .models_lstm import lstmwithattention
-    if isinstance(model, lstmwithattention):
-        raise L.AbdError(f"{what} run the abd_amd smallcnn only, got lstmwithattention (DESIGN.md §5)")
+    from .models_rnn import RNN
+    if isinstance(model, (lstmwithattention, RNN)):
+        raise L.AbdError(f"{what} run the abd_amd smallcnn only, got {type(model).__name__} (DESIGN.md §5)")
 
 
 def _flat_state(model, device):

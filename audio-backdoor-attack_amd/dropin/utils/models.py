@@ -1,8 +1,8 @@
 """Drop-in for utils/models.py.
 
-``smallcnn`` (utils/models.py:17-65, the BASELINE model) and ``lstmwithattention``
-(utils/models.py:180-228) run on libabd.  The other backbones
-(largecnn, smalllstm, RNN, ResNet -- out of scope) are the
+``smallcnn`` (utils/models.py:17-65, the BASELINE model), ``lstmwithattention``
+(utils/models.py:180-228) and ``RNN`` (utils/models.py:231-257) run on libabd.  The other backbones
+(largecnn, smalllstm, ResNet -- out of scope) are the
 reference's own classes, loaded from the checkout behind this package; the accelerated
 ``train()`` / ``test()`` refuse them with an AbdError rather than silently running PyTorch.
 """
@@ -13,16 +13,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import _root  # noqa: F401,E402
 from abd_amd.models import smallcnn  # noqa: F401,E402
 from abd_amd.models_lstm import lstmwithattention  # noqa: F401,E402
+from abd_amd.models_rnn import RNN  # noqa: F401,E402
 
 from . import reference_module  # noqa: E402
 
-_OTHERS = ("largecnn", "smalllstm", "RNN", "ResNet", "ResidualBlock")
+_OTHERS = ("largecnn", "smalllstm", "ResNet", "ResidualBlock")
 
 
 def _missing(name):
     def make(*a, **k):
         raise NotImplementedError(f"{name}: no reference utils/models.py on sys.path to take it from "
-                                  "(abd_amd accelerates smallcnn and lstmwithattention only)")
+                                  "(abd_amd accelerates smallcnn, lstmwithattention and RNN only)")
     return make
 
 

@@ -834,3 +834,84 @@ def lstmattn_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor],
 def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics, num_classes,
       adam_step, lr, beta1, beta2, eps, seed, counter, mask=None):
     return x.new_empty((x.shape[0], num_classes))
+
+
+# --------------------------------------------------------------------------- RNN
+_RNN_NETS: dict = {}
+
+
+def _rnn_net(T: int, F: int, K: int):
+    """A cached libabd RNN handle for one geometry (shapes only, no device state)."""
+    key = (int(T), int(F), int(K))
+    h = _RNN_NETS.get(key)
+    if h is None:
+        h = C.c_void_p()
+        L.check(L.lib().abd_rnn_create(key[0], key[1], key[2], C.byref(h)), "abd_rnn_create")
+        _RNN_NETS[key] = h
+    return h
+
+
+def _rnn_eval(x, params, num_classes, labels, indicators, metrics):
+    L.require_device(x, "RNN input")
+    B, T, F = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    h = _rnn_net(T, F, num_classes)
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
+    ws = _ws(L.lib().abd_rnn_workspace_bytes(h, B), x.device)
+    L.check(L.lib().abd_rnn_eval(h, x.data_ptr(), B, params.data_ptr(), _ptr(labels), _ptr(indicators),
+                                 out.data_ptr(), _ptr(metrics), ws.data_ptr(), ws.numel(),
+                                 L.stream_ptr(x.device)), "abd_rnn_eval")
+    return out
+
+
+@torch.library.custom_op("abd::rnn_eval", mutates_args=())
+def rnn_eval(x: Tensor, params: Tensor, num_classes: int) -> Tensor:
+    """Forward of RNN (3-layer 768-wide LSTM + fc on the last step): (B, 1, T, F) -> logits (B, K)."""
+    return _rnn_eval(x, params, num_classes, None, None, None)
+
+
+@rnn_eval.register_fake
+def _(x, params, num_classes):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::rnn_eval_metrics", mutates_args=("metrics",))
+def rnn_eval_metrics(x: Tensor, params: Tensor, num_classes: int, labels: Tensor, indicators: Optional[Tensor],
+                     metrics: Tensor) -> Tensor:
+    """The forward plus test()'s loss / accuracy / ASR counters accumulated into metrics (int64[8]);
+    returns the logits."""
+    return _rnn_eval(x, params, num_classes, labels, indicators, metrics)
+
+
+@rnn_eval_metrics.register_fake
+def _(x, params, num_classes, labels, indicators, metrics):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::rnn_train_step", mutates_args=("params", "grads", "exp_avg", "exp_avg_sq", "metrics"))
+def rnn_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor], params: Tensor, grads: Tensor,
+                   exp_avg: Tensor, exp_avg_sq: Tensor, metrics: Tensor, num_classes: int, adam_step: int,
+                   lr: float, beta1: float, beta2: float, eps: float) -> Tensor:
+    """One fused train() iteration of RNN on the device; returns the batch's logits (B, K).
+    adam_step >= 1 applies torch.optim.Adam (that step index); 0 leaves params untouched."""
+    L.require_device(x, "RNN input")
+    B, T, F = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    h = _rnn_net(T, F, num_classes)
+    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
+    a = L.RnnArgs()
+    a.x, a.batch = x.data_ptr(), B
+    a.labels, a.indicators = labels.data_ptr(), _ptr(indicators)
+    a.params, a.grads = params.data_ptr(), grads.data_ptr()
+    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    a.lr, a.beta1, a.beta2, a.eps = float(lr), float(beta1), float(beta2), float(eps)
+    a.adam_step, a.do_update = int(adam_step), 1 if adam_step > 0 else 0
+    a.logits_out, a.metrics, a.grad_scale = out.data_ptr(), metrics.data_ptr(), 1.0
+    ws = _ws(L.lib().abd_rnn_workspace_bytes(h, B), x.device)
+    L.check(L.lib().abd_rnn_train_step(h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
+            "abd_rnn_train_step")
+    return out
+
+
+@rnn_train_step.register_fake
+def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, metrics, num_classes, adam_step, lr, beta1, beta2,
+      eps):
+    return x.new_empty((x.shape[0], num_classes))

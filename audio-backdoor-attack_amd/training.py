@@ -21,10 +21,11 @@ import torch.nn as nn
 from . import _lib as L
 from .models import smallcnn, dropout_seed
 from .models_lstm import lstmwithattention
+from .models_rnn import RNN
 from .resident import resident_batches
 
 # the models whose train() / test() steps run on libabd
-ACCELERATED = (smallcnn, lstmwithattention)
+ACCELERATED = (smallcnn, lstmwithattention, RNN)
 
 
 def require_smallcnn(model, what: str):
@@ -159,7 +160,8 @@ def train_step(model: smallcnn, x, labels, indicators, adam: AdamBinding | None,
 
     row_offset: global batch row of x[0] (data parallelism: dropout masks hash the global row).
     bn_sync: a parallel_dp.SyncBatchNorm (synchronised BatchNorm statistics) or None.
-    smallcnn only (lstmwithattention: lstm_train_step; it has no data-parallel / SyncBN step)."""
+    smallcnn only (lstmwithattention: lstm_train_step, RNN: rnn_train_step; neither has a data-parallel /
+    SyncBN step)."""
     require_smallcnn(model, "train_step (the smallcnn / data-parallel step)")
     eng = model.engine(x)
     B = x.shape[0]
@@ -235,12 +237,45 @@ def lstm_train_step(model: lstmwithattention, x, labels, indicators, adam: AdamB
     return a
 
 
+def rnn_train_step(model: RNN, x, labels, indicators, adam: AdamBinding | None, metrics: torch.Tensor | None,
+                   do_update=True, grad_scale=1.0, logits_out=None):
+    """One fused device step of RNN (forward + CE + backward [+ Adam]) through the C ABI."""
+    x = model._prepare(x)
+    eng = model.engine(x)
+    B = x.shape[0]
+    a = model._args(eng, x, B)
+    a.labels = labels.data_ptr() if labels is not None else None
+    a.indicators = indicators.data_ptr() if indicators is not None else None
+    if adam is not None:
+        a.exp_avg, a.exp_avg_sq = eng.exp_avg.data_ptr(), eng.exp_avg_sq.data_ptr()
+        a.lr, (a.beta1, a.beta2), a.eps = adam.lr, adam.betas, adam.eps
+        if do_update:
+            adam.step += 1
+            a.adam_step = adam.step
+            a.do_update = 1
+    if metrics is not None:
+        a.metrics = metrics.data_ptr()
+    if logits_out is not None:
+        a.logits_out = logits_out.data_ptr()
+    a.grad_scale = float(grad_scale)
+    ws = eng.workspace(B)
+    eng.last_train_token = -1   # the step consumes the workspace a pending autograd backward would read
+    rc = L.lib().abd_rnn_train_step(eng.h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
+    L.check(rc, "abd_rnn_train_step")
+    return a
+
+
 def op_train_step(model: smallcnn | lstmwithattention, x, labels, indicators, adam: AdamBinding,
                   metrics: torch.Tensor):
     """train()'s per-batch step through the model's custom op, ``abd::smallcnn_train_step`` or
     ``abd::lstmattn_train_step`` (ops.py)."""
     from . import ops  # noqa: F401  (registers torch.ops.abd)
     eng = model.engine(x)
+    if isinstance(model, RNN):
+        adam.step += 1
+        torch.ops.abd.rnn_train_step(x, labels, indicators, eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, metrics,
+                                     eng.K, adam.step, adam.lr, adam.betas[0], adam.betas[1], adam.eps)
+        return
     if isinstance(model, lstmwithattention):
         hm = model.step_mask(x.shape[0], x.device)
         adam.step += 1
@@ -282,7 +317,7 @@ def read_metrics(m: torch.Tensor):
 
 
 def _unsupported(model):
-    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn / lstmwithattention + Adam + CrossEntropyLoss "
+    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn / lstmwithattention / RNN + Adam + CrossEntropyLoss "
                      f"hot path only; got {type(model).__name__} (other models are out of scope, see DESIGN.md)")
 
 
@@ -317,7 +352,9 @@ def _eval_batches(model, loader, dev, dict_items):
     n = 0
     for x, y, ind in _batches(loader, dev, dict_items):
         eng = model.engine(x)
-        if isinstance(model, lstmwithattention):
+        if isinstance(model, RNN):
+            torch.ops.abd.rnn_eval_metrics(x, eng.params, eng.K, y, ind, metrics)
+        elif isinstance(model, lstmwithattention):
             torch.ops.abd.lstmattn_eval_metrics(x, eng.params, eng.running, eng.K, y, ind, metrics)
         else:
             torch.ops.abd.smallcnn_eval_metrics(x, eng.params, eng.running, eng.K, model.gemm_precision, y, ind,
@@ -426,7 +463,12 @@ def reference_module_state(model: smallcnn | lstmwithattention) -> dict:
                 prm.grad = None
         ref.add_module(name, c)
     ref.train(model.training)
-    return ref.__dict__.copy()
+    state = ref.__dict__.copy()
+    if isinstance(model, RNN):
+        # utils/models.py:235-239: plain attributes its forward reads (h0 / c0 are built on self.device)
+        state.update(hidden_size=model.hidden_size, num_layers=model.num_layers,
+                     device=next(model.parameters()).device)
+    return state
 
 
 def reference_pickle_object(model: smallcnn | lstmwithattention, module: str = "utils.models", name: str = "smallcnn"):
@@ -445,13 +487,15 @@ def reference_pickle_object(model: smallcnn | lstmwithattention, module: str = "
 
 
 def save_reference_checkpoint(model, path):
-    """torch.save in the reference's format: abd smallcnn / lstmwithattention -> a pickle of the
+    """torch.save in the reference's format: abd smallcnn / lstmwithattention / RNN -> a pickle of the
     utils.models class of the same name; any other module is saved as is (the reference's behaviour)."""
     if isinstance(model, smallcnn):
         torch.save(reference_pickle_object(model), path, pickle_module=_GlobalPickleModule())
     elif isinstance(model, lstmwithattention):
         torch.save(reference_pickle_object(model, name="lstmwithattention"), path,
                    pickle_module=_GlobalPickleModule())
+    elif isinstance(model, RNN):
+        torch.save(reference_pickle_object(model, name="RNN"), path, pickle_module=_GlobalPickleModule())
     else:
         torch.save(model, path)
 

@@ -780,6 +780,77 @@ int abd_lstmattn_eval(abd_lstmattn* net, const float* x, int64_t batch, const fl
                       float* logits, int64_t* metrics, void* workspace, size_t workspace_bytes,
                       abd_stream_t stream);
 
+/* ------------------------------------------------------------------ RNN
+ * Replaces utils/models.py:231-257 RNN(num_classes, time_len): nn.LSTM(time_len, 768, 3, batch_first)
+ * from zero initial states, nn.Linear(768, num_classes) on the last time step; forward / backward and
+ * the train() / test() inner steps.  Input (B, 1, T, F) fp32 with F = time_len; raw logits out.  The
+ * model has no BatchNorm and no dropout, so train and eval forwards are the same computation.
+ *
+ * Parameters live in ONE flat fp32 buffer in named_parameters() order, 14 tensors:
+ * lstm.{weight_ih, weight_hh, bias_ih, bias_hh}_l0, _l1, _l2, then fc.weight, fc.bias.
+ *
+ * Every product is fp32: an LDS-tiled v_mfma_f32_32x32x2_f32 GEMM (input projections of all B*T rows,
+ * data and weight gradients, fc) and one launch per time step for the recurrence, whose workgroups own
+ * the four gates of their hidden units (W_hh, 9.4 MB per layer, is streamed; it does not fit LDS).  The
+ * weight gradients' B*T reduction is cut into slices summed in slice order; there are no float atomics
+ * and two calls on equal inputs give bit-equal results.  The entry points allocate nothing, never
+ * synchronise and take nothing from host memory but their arguments.
+ *
+ * The workspace keeps h, c and the four activated gates of every layer and step for BPTT:
+ * 3 * B*T * (768 + 768 + 3072) floats and a (B*T, 768) gradient buffer, about 1.5 GB at B = 256,
+ * T = 100; abd_rnn_workspace_bytes reports the exact size.  backward overwrites the saved gates with
+ * the gate gradients, so it runs once per forward. */
+typedef struct abd_rnn abd_rnn;
+
+/* abd_lstmattn_args without the dropout and running-statistics fields */
+typedef struct abd_rnn_args {
+  const float* x;            /* (B,1,T,F)                                      */
+  const int64_t* labels;     /* (B)                                            */
+  const int64_t* indicators; /* (B) poison indicator, NULL = none              */
+  int64_t batch;
+  float* params;             /* flat                                           */
+  float* grads;              /* flat (written)                                 */
+  float* exp_avg;            /* flat Adam m                                    */
+  float* exp_avg_sq;         /* flat Adam v                                    */
+  int64_t adam_step;         /* step index after increment (1-based)           */
+  float lr, beta1, beta2, eps;
+  int do_update;             /* 0: forward/backward only (grads), 1: + Adam    */
+  float* logits_out;         /* optional (B,K)                                 */
+  int64_t* metrics;          /* optional ABD_METRICS_WORDS accumulators        */
+  float grad_scale;          /* multiplies the loss gradient and weights
+                              * metrics[0]'s batch-mean loss                   */
+} abd_rnn_args;
+
+/* ABD_E_UNSUPPORTED outside 1 <= F <= 128, 1 <= T <= 1024 */
+int abd_rnn_create(int T, int F, int num_classes, abd_rnn** net);
+void abd_rnn_destroy(abd_rnn* net);
+int64_t abd_rnn_param_count(const abd_rnn* net);
+int abd_rnn_param_offsets(const abd_rnn* net, int64_t* offsets /* 15 */);
+/* kernel geometry (tests): 0 batch rows of a recurrent workgroup, 1 / 2 edge of the small / large GEMM
+ * block tile, 3 least rows of a weight-gradient slice, 4 rows above which column sums take two stages,
+ * 5 least count of large tiles for which the large tile is used; -1 otherwise */
+int abd_rnn_tile_info(int what);
+size_t abd_rnn_workspace_bytes(const abd_rnn* net, int64_t batch);
+/* Byte offset of a saved activation inside the workspace (tests), -1 for an unknown name:
+ * h1 h2 h3 c1 c2 c3 ((B,T,768) per layer), gates1 gates2 gates3 ((B*T,3072) activated i f g o after
+ * forward), logits dlogits rowinfo. */
+int64_t abd_rnn_workspace_offset(const abd_rnn* net, int64_t batch, const char* name);
+/* forward keeps every activation in the workspace and writes the logits to a->logits_out (if set).
+ * backward consumes d(logits) and must follow a forward on the same workspace. */
+int abd_rnn_forward(abd_rnn* net, const abd_rnn_args* a, void* workspace, size_t workspace_bytes,
+                    abd_stream_t stream);
+int abd_rnn_backward(abd_rnn* net, const abd_rnn_args* a, const float* dlogits, void* workspace,
+                     size_t workspace_bytes, abd_stream_t stream);
+/* forward, cross entropy (mean over the batch) with the ABD_METRICS_WORDS counters, backward, and
+ * abd_adam_f32 on the flat buffer when do_update; d(logits) in torch's log_softmax / nll_loss
+ * arithmetic as in abd_lstmattn_train_step.  labels are required (ABD_E_INVALID). */
+int abd_rnn_train_step(abd_rnn* net, const abd_rnn_args* a, void* workspace, size_t workspace_bytes,
+                       abd_stream_t stream);
+/* Writes the logits and, if labels != NULL, accumulates the counters like test(). */
+int abd_rnn_eval(abd_rnn* net, const float* x, int64_t batch, const float* params, const int64_t* labels,
+                 const int64_t* indicators, float* logits, int64_t* metrics, void* workspace,
+                 size_t workspace_bytes, abd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
