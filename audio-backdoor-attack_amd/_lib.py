@@ -16,11 +16,15 @@ LIB_PATH = os.environ.get("ABD_LIB", os.path.join(HERE, "libabd.so"))
 ABD_MEL_HTK, ABD_MEL_SLANEY = 0, 1
 ABD_PAD_REFLECT, ABD_PAD_CONSTANT = 0, 1
 INJECT_NONE, INJECT_ADD, INJECT_SNR_WINDOW, INJECT_HALF_MIX, INJECT_DEPLOY, INJECT_DEPLOY_CLAMP = 0, 1, 2, 3, 4, 5
+MFCC_INFO = {"fast": 0, "ppb": 1, "chunks": 2, "mel_path": 3, "dct_kernel": 4, "bwd_ok": 5}   # ABD_MFCC_INFO_*
+MFCC_MEL_PATHS = ("generic", "half_slot", "segmented", "blue_slots")                           # ABD_MFCC_MEL_*
+MFCC_DCT_KERNELS = ("plain", "lds", "mfma1", "mfma2", "mfma3")                                 # ABD_MFCC_DCT_*
 METRICS_WORDS = 8
 
 EXPORTS = (
     "abd_last_error", "abd_version",
     "abd_mfcc_plan_create", "abd_mfcc_plan_destroy", "abd_mfcc_plan_frames", "abd_mfcc_plan_describe",
+    "abd_mfcc_plan_info",
     "abd_mfcc_workspace_bytes", "abd_mfcc_f32", "abd_mfcc_rows_f32", "abd_gather_rows_f32", "abd_inject_waveform_f32", "abd_inject_workspace_bytes",
     "abd_inject_row_scales",
     "abd_pydub_overlay_i16", "abd_mfcc_deploy_backward_workspace_bytes", "abd_mfcc_deploy_backward",
@@ -204,6 +208,7 @@ def _declare(lib):
         "abd_mfcc_plan_destroy": (None, [vp]),
         "abd_mfcc_plan_frames": (i32, [vp]),
         "abd_mfcc_plan_describe": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "abd_mfcc_plan_info": (i32, [vp, i32]),
         "abd_mfcc_workspace_bytes": (sz, [vp, i64]),
         "abd_mfcc_f32": (i32, [vp, vp, i64, vp, i64, C.POINTER(Inject), vp, vp, sz, vp]),
         "abd_mfcc_rows_f32": (i32, [vp, vp, i64, vp, i64, C.POINTER(Inject), vp, vp, vp, sz, vp]),

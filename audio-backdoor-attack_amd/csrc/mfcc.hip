@@ -2170,7 +2170,10 @@ int choose_bluestein_M(int N) {
   const int lo = 2 * N - 1;
   int best = 0;
   double bc = 1e300;
-  for (int m = lo; m <= 4 * lo; ++m) {
+  // the cheapest length among those a block can hold: for n_fft 3001 .. 3071 a cheaper length above the cap
+  // (6250 or 6400 against 6144) would refuse a geometry that fits.  lo above the cap: refused by the caller.
+  const int hi = lo <= kMaxComplexPerBlock ? std::min(4 * lo, kMaxComplexPerBlock) : 4 * lo;
+  for (int m = lo; m <= hi; ++m) {
     if (!smooth235(m)) continue;
     const double c = fft_cost(m);
     if (c < bc) {
@@ -2191,6 +2194,20 @@ void host_fft(std::vector<std::complex<double>>& x) {  // forward, O(M^2) fine a
     y[k] = acc;
   }
   x.swap(y);
+}
+
+size_t dct_lds_bytes(const MfccDev& d) {
+  return ((size_t)d.n_mels * d.n_mfcc + (size_t)kTT2 * d.n_mels) * sizeof(float);
+}
+
+// The dB + DCT kernel of a plan (ABD_MFCC_DCT_*): the matrix cores where the plan built their B
+// fragments (dct_tiles), else the LDS kernel where its float4 rows and 64 KiB tile allow, else the plain
+// one.  out_aligned: the caller's output is 16-byte aligned (its rows are T * n_mfcc floats: 16 B
+// apart too when n_mfcc % 4 == 0) -- known at launch only.
+int choose_dct_kernel(const MfccDev& d, bool out_aligned) {
+  if (d.dct_tiles > 0) return ABD_MFCC_DCT_MFMA1 + std::min(d.dct_tiles, 3) - 1;
+  if (d.n_mfcc % 4 == 0 && dct_lds_bytes(d) <= 64 * 1024 && out_aligned && d.dct_lds) return ABD_MFCC_DCT_LDS;
+  return ABD_MFCC_DCT_PLAIN;
 }
 
 }  // namespace
@@ -2642,6 +2659,23 @@ int abd_mfcc_plan_describe(const abd_mfcc_plan* plan, int* fft_size, int* bluest
   return ABD_OK;
 }
 
+int abd_mfcc_plan_info(const abd_mfcc_plan* plan, int what) {
+  if (!plan) return -1;
+  const MfccDev& d = plan->dev;
+  switch (what) {
+    case ABD_MFCC_INFO_FAST: return d.fast;
+    case ABD_MFCC_INFO_PPB: return d.ppb;
+    case ABD_MFCC_INFO_CHUNKS: return d.chunks;
+    case ABD_MFCC_INFO_MEL_PATH:
+      if (!d.fast) return ABD_MFCC_MEL_GENERIC;
+      if (d.bluestein && d.mel3_w != nullptr) return ABD_MFCC_MEL_BLUE_SLOTS;
+      return d.nseg > 0 ? ABD_MFCC_MEL_SEGMENTED : ABD_MFCC_MEL_HALF_SLOT;
+    case ABD_MFCC_INFO_DCT_KERNEL: return choose_dct_kernel(d, true);
+    case ABD_MFCC_INFO_BWD_OK: return d.bwd_ok;
+    default: return -1;
+  }
+}
+
 size_t abd_mfcc_workspace_bytes(const abd_mfcc_plan* plan, int64_t batch) {
   if (!plan) return 0;
   const MfccDev& d = plan->dev;
@@ -2747,14 +2781,14 @@ int abd_mfcc_rows_f32(const abd_mfcc_plan* plan, const float* wave, int64_t row_
   abd::prof_end(abd::PH_STFT_MEL, s);
   ABD_LAUNCH_CHECK();
   abd::prof_begin(abd::PH_DB_DCT, s);
-  const size_t dct_lds = ((size_t)d.n_mels * d.n_mfcc + (size_t)kTT2 * d.n_mels) * sizeof(float);
-  if (d.dct_tiles > 0) {
+  const size_t dct_lds = dct_lds_bytes(d);
+  const int dk = choose_dct_kernel(d, (reinterpret_cast<uintptr_t>(out) & 15) == 0);
+  if (dk >= ABD_MFCC_DCT_MFMA1) {
     const dim3 g((unsigned)batch, (unsigned)((d.T + 63) / 64));
-    if (d.dct_tiles == 1) db_dct_mfma_kernel<1><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out, out_rows);
-    else if (d.dct_tiles == 2) db_dct_mfma_kernel<2><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out, out_rows);
+    if (dk == ABD_MFCC_DCT_MFMA1) db_dct_mfma_kernel<1><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out, out_rows);
+    else if (dk == ABD_MFCC_DCT_MFMA2) db_dct_mfma_kernel<2><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out, out_rows);
     else db_dct_mfma_kernel<3><<<g, dim3(kThreads), 0, s>>>(d, ws_db, ws_max, ij, out, out_rows);
-  } else if (d.n_mfcc % 4 == 0 && dct_lds <= 64 * 1024 &&
-      (reinterpret_cast<uintptr_t>(out) & 15) == 0 && d.dct_lds) {  // rows are T * n_mfcc floats: 16 B apart too
+  } else if (dk == ABD_MFCC_DCT_LDS) {
     db_dct_lds_kernel<<<dim3((unsigned)batch, (unsigned)((d.T + kTT2 - 1) / kTT2)), dim3(kThreads), dct_lds, s>>>(
         d, ws_db, ws_max, ij, out, out_rows);
   } else {

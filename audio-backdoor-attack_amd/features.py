@@ -62,8 +62,11 @@ class MfccPlan:
         m, blue, npass = C.c_int(), C.c_int(), C.c_int()
         rad = (C.c_int * 16)()
         L.check(L.lib().abd_mfcc_plan_describe(self._h, C.byref(m), C.byref(blue), C.byref(npass), rad), "describe")
+        info = {k: int(L.lib().abd_mfcc_plan_info(self._h, i)) for k, i in L.MFCC_INFO.items()}
         return {"fft_size": m.value, "bluestein": bool(blue.value), "radices": list(rad[:npass.value]),
-                "n_frames": self.n_frames}
+                "n_frames": self.n_frames, "fast": bool(info["fast"]), "ppb": info["ppb"], "chunks": info["chunks"],
+                "mel_path": L.MFCC_MEL_PATHS[info["mel_path"]], "dct_kernel": L.MFCC_DCT_KERNELS[info["dct_kernel"]],
+                "bwd_ok": bool(info["bwd_ok"])}
 
     def workspace_bytes(self, batch: int) -> int:
         return int(L.lib().abd_mfcc_workspace_bytes(self._h, int(batch)))

@@ -57,6 +57,19 @@ int abd_mfcc_plan_frames(const abd_mfcc_plan* plan);
 int abd_mfcc_plan_describe(const abd_mfcc_plan* plan, int* fft_size, int* bluestein,
                            int* n_passes, int* radices /* >= 16 ints */);
 size_t abd_mfcc_workspace_bytes(const abd_mfcc_plan* plan, int64_t batch);
+/* Which kernels a plan runs (tests): what = ABD_MFCC_INFO_*; -1 for an unknown what or a NULL plan.
+ *   FAST        1 = a specialised STFT kernel (n_fft 400, 2048, 1103), 0 = the runtime-radix one
+ *   PPB, CHUNKS frame pairs per work item, work items per utterance
+ *   MEL_PATH    ABD_MFCC_MEL_*: the runtime-radix kernel's loop, or the specialised kernels' half-filter
+ *               slots, filter segments, or Bluestein slot table
+ *   DCT_KERNEL  ABD_MFCC_DCT_*, for a 16-byte aligned output (an unaligned one takes PLAIN instead of LDS)
+ *   BWD_OK      1 = every bin lies in at most two mel filters (abd_mfcc_deploy_backward needs it) */
+enum { ABD_MFCC_INFO_FAST = 0, ABD_MFCC_INFO_PPB = 1, ABD_MFCC_INFO_CHUNKS = 2, ABD_MFCC_INFO_MEL_PATH = 3,
+       ABD_MFCC_INFO_DCT_KERNEL = 4, ABD_MFCC_INFO_BWD_OK = 5 };
+enum { ABD_MFCC_MEL_GENERIC = 0, ABD_MFCC_MEL_HALF_SLOT = 1, ABD_MFCC_MEL_SEGMENTED = 2, ABD_MFCC_MEL_BLUE_SLOTS = 3 };
+enum { ABD_MFCC_DCT_PLAIN = 0, ABD_MFCC_DCT_LDS = 1, ABD_MFCC_DCT_MFMA1 = 2, ABD_MFCC_DCT_MFMA2 = 3,
+       ABD_MFCC_DCT_MFMA3 = 4 };
+int abd_mfcc_plan_info(const abd_mfcc_plan* plan, int what);
 
 /* Trigger injection fused into the feature load / epilogue.
  *   ADD        x + trigger                      ultrasonic.py:75,96 (trigger from
