@@ -1,0 +1,170 @@
+"""The flat-buffer engine shared by ``models_lstm.lstmwithattention`` and ``models_rnn.RNN``.
+
+Both models keep their parameters in ONE flat device buffer in ``PARAM_ORDER`` (and their BatchNorm running
+statistics, if any, in a second one), drive a family of C entry points that differ only in their prefix
+(``abd_lstmattn_*`` / ``abd_rnn_*``), and keep the activations of a train-mode forward in a shared workspace
+that the backward of the same step reads.  ``models.smallcnn`` has the same shape but also carries the bf16
+modes, data parallelism and the defence hooks; it keeps its own engine.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+
+
+def net_handle(prefix: str, T: int, F: int, K: int):
+    h = C.c_void_p()
+    L.check(getattr(L.lib(), f"{prefix}_create")(int(T), int(F), int(K), C.byref(h)), f"{prefix}_create")
+    return h
+
+
+class FlatEngine:
+    """libabd network handle + flat device buffers for one (T, F, K) geometry.  running / nbt: the sizes of
+    the BatchNorm running-statistics and num_batches_tracked buffers, 0 for a model without BatchNorm."""
+
+    def __init__(self, prefix: str, n_params: int, T: int, F: int, K: int, device: torch.device, running: int = 0,
+                 nbt: int = 0):
+        self.prefix, self.n_params = prefix, n_params
+        self.T, self.F, self.K = T, F, K
+        self.device = device
+        self.h = net_handle(prefix, T, F, K)
+        offs = (C.c_int64 * (n_params + 1))()
+        self.call("param_offsets", offs)
+        self.offsets = list(offs)
+        self.n = self.offsets[-1]
+        self.params = torch.empty(self.n, dtype=torch.float32, device=device)
+        self.grads = torch.zeros(self.n, dtype=torch.float32, device=device)
+        self.exp_avg = None
+        self.exp_avg_sq = None
+        self.running = torch.empty(running, dtype=torch.float32, device=device) if running else None
+        self.nbt = torch.zeros(nbt, dtype=torch.int64, device=device) if nbt else None
+        self._ws = None
+        self.token = 0
+        self.last_train_token = -1
+
+    def call(self, name: str, *args):
+        """abd_<model>_<name>(handle, *args), checked."""
+        L.check(getattr(L.lib(), f"{self.prefix}_{name}")(self.h, *args), f"{self.prefix}_{name}")
+
+    def workspace(self, batch):
+        """The shared activation workspace, grown on demand (the old one is released first: RNN's is about
+        5.9 KB per (row, step), 1.5 GB at B = 256, T = 100)."""
+        need = getattr(L.lib(), f"{self.prefix}_workspace_bytes")(self.h, int(batch))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def views(self, buf):
+        return [buf[self.offsets[i]:self.offsets[i + 1]] for i in range(self.n_params)]
+
+    def __del__(self):
+        try:
+            if self.h and self.h.value:
+                getattr(L.lib(), f"{self.prefix}_destroy")(self.h)
+        except Exception:
+            pass
+
+
+class FlatModule:
+    """Mixin of an nn.Module whose parameters live in a FlatEngine.  The class sets PARAM_ORDER, RUNNING_ORDER
+    (((BatchNorm name, channels), ...), empty without BatchNorm), ARGS (the C args struct), ENGINE
+    ((model, T, F, device) -> FlatEngine), BACKWARD_ORDER (the message of a backward out of turn) and
+    BACKWARD_CONSUMES (backward overwrites what the forward saved, so a token serves once)."""
+
+    RUNNING_ORDER = ()
+    BACKWARD_CONSUMES = False
+
+    def _param_list(self):
+        d = dict(self.named_parameters())
+        return [d[n] for n in self.PARAM_ORDER]
+
+    def _running_slots(self, eng):
+        """(index, BatchNorm module, its running_mean view, its running_var view) per RUNNING_ORDER entry."""
+        o = 0
+        for i, (name, c) in enumerate(self.RUNNING_ORDER):
+            yield i, getattr(self, name), eng.running[o:o + c], eng.running[o + c:o + 2 * c]
+            o += 2 * c
+
+    def _bound(self, eng) -> bool:
+        if eng is None:
+            return False
+        base = eng.params.data_ptr()
+        for p, off in zip(self._param_list(), eng.offsets):
+            if p.data.data_ptr() != base + 4 * off or p.device != eng.device:
+                return False
+        for _, bn, mean, var in self._running_slots(eng):
+            if bn.running_mean.data_ptr() != mean.data_ptr() or bn.running_var.data_ptr() != var.data_ptr():
+                return False
+        return True
+
+    def _bind(self, T: int, F: int, device):
+        """The engine for this geometry and device: the bound one, or a new one the parameters, the BatchNorm
+        buffers and every nn.LSTM child's cached weight list are re-homed into."""
+        eng = self._engine
+        if eng is not None and (eng.T, eng.F) == (T, F) and eng.device == device and self._bound(eng):
+            return eng
+        new = self.ENGINE(self, T, F, device)
+        with torch.no_grad():
+            for p, v in zip(self._param_list(), new.views(new.params)):
+                v.copy_(p.data.reshape(-1))
+                p.data = v.view(p.shape)
+            for i, bn, mean, var in self._running_slots(new):
+                mean.copy_(bn.running_mean)
+                var.copy_(bn.running_var)
+                bn.running_mean, bn.running_var = mean, var
+                new.nbt[i].copy_(bn.num_batches_tracked)
+                bn.num_batches_tracked = new.nbt[i]
+        # nn.LSTM caches a flattened copy of its weights for the vendor RNN kernels; they are views now
+        for rnn in self.children():
+            if isinstance(rnn, torch.nn.LSTM):
+                rnn._flat_weights = [getattr(rnn, n) for n in rnn._flat_weights_names]
+        self._engine = new
+        return new
+
+    def _args(self, eng, x, B):
+        a = self.ARGS()
+        a.x = x.data_ptr()
+        a.batch = B
+        a.params = eng.params.data_ptr()
+        a.grads = eng.grads.data_ptr()
+        if eng.running is not None:
+            a.running = eng.running.data_ptr()
+            a.num_batches_tracked = eng.nbt.data_ptr()
+        a.grad_scale = 1.0
+        return a
+
+    def hip_backward(self, x, dlogits, token):
+        eng = self._engine
+        if eng is None or token != eng.last_train_token:
+            raise L.AbdError(self.BACKWARD_ORDER)
+        if self.BACKWARD_CONSUMES:
+            eng.last_train_token = -1
+        B = x.shape[0]
+        ws = eng.workspace(B)
+        a = self._args(eng, x, B)
+        dl = dlogits.contiguous()
+        eng.call("backward", C.byref(a), dl.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
+        return eng.views(eng.grads)
+
+
+class FlatFunction(torch.autograd.Function):
+    """model.hip_train_forward(x) with model.hip_backward as its gradient, for either model."""
+
+    @staticmethod
+    def forward(ctx, x, model, *params):
+        out = model.hip_train_forward(x)
+        ctx.model = model
+        ctx.token = model._engine.last_train_token
+        ctx.save_for_backward(x)
+        ctx.shapes = [p.shape for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, dl):
+        (x,) = ctx.saved_tensors
+        gs = ctx.model.hip_backward(x, dl, ctx.token)
+        return (None, None, *[g.view(s).clone() for g, s in zip(gs, ctx.shapes)])

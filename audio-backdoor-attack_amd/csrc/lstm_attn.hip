@@ -50,10 +50,9 @@ struct Offs {
   __host__ __device__ int64_t operator[](int i) const { return v[i]; }
 };
 
-// colsum_kernel, ce_kernel, metrics_kernel (shared with rnn.hip)
-#include "reduce_ce.inc"
-
-__device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
+// shared with rnn.hip: backward cell, GemmArgs and its three forms, the host helpers; colsum_kernel,
+// ce_kernel, metrics_kernel
+#include "lstm_common.inc"
 
 // the dropout hash of the smallcnn kernels: keep with probability 1 - p
 __device__ __forceinline__ bool keep_hash(uint64_t seed, uint64_t stream, uint64_t idx, float p) {
@@ -66,22 +65,8 @@ __device__ __forceinline__ bool keep_hash(uint64_t seed, uint64_t stream, uint64
   return u >= p;
 }
 
-// ------------------------------------------------------------------ fp32 MFMA GEMM
-// C[m][n] (+)= sum_k A(m,k) B(k,n) (+ bias1[n] + bias2[n]); A(m,k) = A[m*sam + k*sak],
-// B(k,n) = B[kb*sbk + n*sbn].  shift != 0: kb = k + shift when k's step (k % T) + shift stays inside
-// [0, T), else the term is zero (h_{t-1} / h_{t+1} of the weight gradient).  blockIdx.z takes the
-// k-slice [z*kchunk, (z+1)*kchunk) and writes C + z*cz.  One wave per 32x32 tile.
-struct GemmArgs {
-  const float* A;
-  const float* B;
-  float* C;
-  int M, N, K;
-  int64_t sam, sak, sbk, sbn, ldc, cz;
-  const float* bias1;
-  const float* bias2;
-  int accumulate, kchunk, T, shift;
-};
-
+// ------------------------------------------------------------------ fp32 MFMA GEMM (GemmArgs)
+// One wave per 32x32 tile.
 __global__ void __launch_bounds__(64) gemm_kernel(GemmArgs a) {
   const int lane = threadIdx.x;
   const int m = blockIdx.x * 32 + (lane & 31);
@@ -244,13 +229,7 @@ __global__ void __launch_bounds__(kT) lstm_bwd_kernel(LstmArgs a) {
         const float ct = a.c[((int64_t)dir * BT + row) * kHid + u];
         const float cp = (tp >= 0 && tp < a.T) ? a.c[((int64_t)dir * BT + (int64_t)b * a.T + tp) * kHid + u] : 0.0f;
         const float dht = a.dy[row * (2 * kHid) + dir * kHid + u] + dh[r];
-        const float tc = tanhf(ct);
-        const float dct = dc[r] + dht * og * (1.0f - tc * tc);
-        di = dct * gg * ig * (1.0f - ig);
-        df = dct * cp * fg * (1.0f - fg);
-        dgg = dct * ig * (1.0f - gg * gg);
-        dob = dht * tc * og * (1.0f - og);
-        dc[r] = dct * fg;
+        lstm_cell_bwd(ig, fg, gg, og, ct, cp, dht, dc[r], di, df, dgg, dob, dc[r]);
         float* dp = a.dg + ((int64_t)dir * BT + row) * kGates + u;
         dp[0] = di;
         dp[kHid] = df;
@@ -720,12 +699,7 @@ int slabs_for(int64_t N) { return (int)std::max<int64_t>(1, std::min<int64_t>(kM
 
 Layout make_layout(const abd_lstmattn* n, int64_t B) {
   Layout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t r = o;
-    o += (bytes + 255) & ~(size_t)255;
-    return r;
-  };
+  Take take;
   const int64_t BT = B * n->T, N = BT * n->F;
   L.a1 = take(4 * N * kC1);
   L.a2 = take(4 * N);
@@ -758,25 +732,18 @@ Layout make_layout(const abd_lstmattn* n, int64_t B) {
   L.coef = take(4 * 64);
   L.part = take(8 * (size_t)kC1 * kMaxSlabs * kQ);
   // weight-gradient GEMMs: B*T rows of reduction split into slices of >= 256 rows
-  L.ksplit = (int)std::max<int64_t>(1, std::min<int64_t>(64, BT / 256));
-  L.kchunk = (BT + L.ksplit - 1) / L.ksplit;
-  L.kchunk = (L.kchunk + 7) & ~(int64_t)7;
-  L.ksplit = (int)((BT + L.kchunk - 1) / L.kchunk);
+  const Slices sl = plan_slices(BT, 64, 256, 8);
+  L.ksplit = sl.ksplit;
+  L.kchunk = sl.kchunk;
   L.slab = take(4 * (size_t)L.ksplit * kGates * 128);
   L.colp = take(4 * (size_t)64 * kGates);
-  L.total = o;
+  L.total = take.o;
   return L;
 }
 
-struct Ctx {
+struct Ctx : CtxBase {
   const abd_lstmattn* n;
   Layout L;
-  char* ws;
-  hipStream_t s;
-  int64_t B;
-  const float* params;
-  float* grads;
-  template <class Tp> Tp* at(size_t off) const { return reinterpret_cast<Tp*>(ws + off); }
   Offs offs() const {
     Offs o;
     for (int i = 0; i < 35; ++i) o.v[i] = n->off[i];
@@ -793,22 +760,9 @@ int launch_gemm(hipStream_t s, GemmArgs g, int ksplit = 1) {
   return ABD_OK;
 }
 
-// out[cols] (+)= column sums of A (rows x cols, leading dimension ld); two fixed-order stages
-int launch_colsum(const Ctx& c, const float* A, int64_t rows, int64_t cols, int64_t ld, float* out, int accumulate) {
-  const int nb = (int)((cols + kT - 1) / kT);
-  const int S = (cols <= kGates && rows > 512) ? (int)std::min<int64_t>(64, rows / 256) : 1;
-  if (S <= 1) {
-    colsum_kernel<<<dim3(nb, 1), kT, 0, c.s>>>(A, rows, cols, ld, rows, out, 0, accumulate);
-    ABD_LAUNCH_CHECK();
-    return ABD_OK;
-  }
-  const int64_t chunk = (rows + S - 1) / S;
-  float* part = c.at<float>(c.L.colp);
-  colsum_kernel<<<dim3(nb, S), kT, 0, c.s>>>(A, rows, cols, ld, chunk, part, cols, 0);
-  ABD_LAUNCH_CHECK();
-  colsum_kernel<<<dim3(nb, 1), kT, 0, c.s>>>(part, S, cols, cols, S, out, 0, accumulate);
-  ABD_LAUNCH_CHECK();
-  return ABD_OK;
+// out[cols] = column sums of A; two fixed-order stages past 512 rows
+int colsum(const Ctx& c, const float* A, int64_t rows, int64_t cols, int64_t ld, float* out) {
+  return launch_colsum(c, A, rows, cols, ld, out, 0, kGates, 512);
 }
 
 // Raise the kernel's dynamic-LDS limit once per device (bit d of *done = device d has it; devices past
@@ -885,18 +839,7 @@ int lstm_layer_fwd(const Ctx& c, int layer, const float* x, int in, float* y, fl
   LstmArgs la{};
   for (int dir = 0; dir < 2; ++dir) {
     const int64_t* off = c.n->off + p0 + dir * 4;
-    GemmArgs g{};
-    g.A = x;
-    g.B = c.params + off[0];
-    g.C = xp + (int64_t)dir * BT * kGates;
-    g.M = (int)BT;
-    g.N = kGates;
-    g.K = in;
-    g.sam = in;
-    g.sak = 1;
-    g.sbk = 1;
-    g.sbn = in;
-    g.ldc = kGates;
+    GemmArgs g = gemm_nt(x, in, c.params + off[0], xp + (int64_t)dir * BT * kGates, (int)BT, kGates, in);
     g.bias1 = c.params + off[2];
     g.bias2 = c.params + off[3];
     if (int rc = launch_gemm(c.s, g)) return rc;
@@ -936,53 +879,28 @@ int lstm_layer_bwd(const Ctx& c, int layer, const float* x, int in, const float*
     const int64_t* off = c.n->off + p0 + dir * 4;
     const float* dgd = dg + (int64_t)dir * BT * kGates;
     // dW_ih[j][i] = sum_rows dg[row][j] x[row][i]
-    GemmArgs g{};
-    g.A = dgd;
-    g.B = x;
-    g.C = slab;
-    g.M = kGates;
-    g.N = in;
-    g.K = (int)BT;
-    g.sam = 1;
-    g.sak = kGates;
-    g.sbk = in;
-    g.sbn = 1;
-    g.ldc = in;
+    GemmArgs g = gemm_tn(dgd, x, in, slab, kGates, in, BT);
     g.cz = (int64_t)kGates * in;
     g.kchunk = (int)c.L.kchunk;
     if (int rc = launch_gemm(c.s, g, c.L.ksplit)) return rc;
-    if (int rc = launch_colsum(c, slab, c.L.ksplit, (int64_t)kGates * in, (int64_t)kGates * in, c.grads + off[0], 0))
-      return rc;
+    if (int rc = colsum(c, slab, c.L.ksplit, g.cz, g.cz, c.grads + off[0])) return rc;
     // dW_hh[j][k] = sum_rows dg[row][j] h_prev[row][k]; h_prev is the y row one step back in this
     // direction's order (t-1 forward, t+1 reverse), zero at the sequence start
-    g.B = y + dir * kHid;
-    g.N = kHid;
-    g.sbk = 2 * kHid;
-    g.ldc = kHid;
+    g = gemm_tn(dgd, y + dir * kHid, 2 * kHid, slab, kGates, kHid, BT);
     g.cz = (int64_t)kGates * kHid;
+    g.kchunk = (int)c.L.kchunk;
     g.T = c.n->T;
     g.shift = dir ? 1 : -1;
     if (c.n->T > 1) {
       if (int rc = launch_gemm(c.s, g, c.L.ksplit)) return rc;
-      if (int rc = launch_colsum(c, slab, c.L.ksplit, kGates * kHid, kGates * kHid, c.grads + off[1], 0)) return rc;
+      if (int rc = colsum(c, slab, c.L.ksplit, g.cz, g.cz, c.grads + off[1])) return rc;
     } else {
       ABD_HIP(hipMemsetAsync(c.grads + off[1], 0, sizeof(float) * kGates * kHid, c.s));
     }
-    if (int rc = launch_colsum(c, dgd, BT, kGates, kGates, c.grads + off[2], 0)) return rc;
+    if (int rc = colsum(c, dgd, BT, kGates, kGates, c.grads + off[2])) return rc;
     ABD_HIP(hipMemcpyAsync(c.grads + off[3], c.grads + off[2], sizeof(float) * kGates, hipMemcpyDeviceToDevice, c.s));
     // dx[row][i] (+)= sum_j dg[row][j] W_ih[j][i]
-    GemmArgs d{};
-    d.A = dgd;
-    d.B = c.params + off[0];
-    d.C = dx;
-    d.M = (int)BT;
-    d.N = in;
-    d.K = kGates;
-    d.sam = kGates;
-    d.sak = 1;
-    d.sbk = in;
-    d.sbn = 1;
-    d.ldc = in;
+    GemmArgs d = gemm_nn(dgd, kGates, c.params + off[0], dx, (int)BT, in, kGates);
     d.accumulate = dir;
     if (int rc = launch_gemm(c.s, d)) return rc;
   }
@@ -1037,43 +955,10 @@ int run_forward(const Ctx& c, const Fwd& f) {
   return ABD_OK;
 }
 
-int run_ce(const Ctx& c, const int64_t* labels, const int64_t* ind, bool grad, float grad_scale, float* logits_out,
-           int64_t* metrics) {
-  CeArgs ce{};
-  ce.logits = c.at<float>(c.L.logits);
-  ce.labels = labels;
-  ce.ind = ind;
-  ce.dlogits = grad ? c.at<float>(c.L.dlogits) : nullptr;
-  ce.rowinfo = c.at<float>(c.L.rowinfo);
-  ce.logits_out = logits_out;
-  ce.K = c.n->K;
-  ce.scale = grad_scale / (float)c.B;
-  if (!labels && !logits_out) return ABD_OK;
-  ce_kernel<<<(unsigned)c.B, 64, 0, c.s>>>(ce);
-  ABD_LAUNCH_CHECK();
-  if (labels && metrics) {
-    metrics_kernel<<<1, kT, 0, c.s>>>(ce.rowinfo, (int)c.B, metrics, (double)grad_scale);
-    ABD_LAUNCH_CHECK();
-  }
-  return ABD_OK;
-}
-
 // dW[o][i] = sum_b delta[b][o] act[b*act_ld + i], db[o] = sum_b delta[b][o]
 int dense_grads(const Ctx& c, const float* delta, int out, const float* act, int in, int64_t act_ld, int pw) {
-  GemmArgs g{};
-  g.A = delta;
-  g.B = act;
-  g.C = c.grads + c.n->off[pw];
-  g.M = out;
-  g.N = in;
-  g.K = (int)c.B;
-  g.sam = 1;
-  g.sak = out;
-  g.sbk = act_ld;
-  g.sbn = 1;
-  g.ldc = in;
-  if (int rc = launch_gemm(c.s, g)) return rc;
-  return launch_colsum(c, delta, c.B, out, out, c.grads + c.n->off[pw + 1], 0);
+  if (int rc = launch_gemm(c.s, gemm_tn(delta, act, act_ld, c.grads + c.n->off[pw], out, in, c.B))) return rc;
+  return colsum(c, delta, c.B, out, out, c.grads + c.n->off[pw + 1]);
 }
 
 int run_backward(const Ctx& c, const float* x, const float* dlogits) {
@@ -1114,20 +999,7 @@ int run_backward(const Ctx& c, const float* x, const float* dlogits) {
 
 int make_ctx(const abd_lstmattn* net, int64_t B, const float* params, float* grads, void* ws, size_t bytes,
              abd_stream_t stream, Ctx* c) {
-  ABD_CHECK(net != nullptr, ABD_E_INVALID, "NULL network");
-  ABD_CHECK(B >= 1 && B * (int64_t)net->T * kGates * 2 < (1LL << 31), ABD_E_INVALID,
-            "batch %lld outside the kernels' 32-bit row range", (long long)B);
-  ABD_CHECK(params != nullptr, ABD_E_INVALID, "NULL params");
-  c->n = net;
-  c->L = make_layout(net, B);
-  ABD_CHECK(ws != nullptr && bytes >= c->L.total, ABD_E_WORKSPACE, "workspace %zu < %zu bytes", bytes, c->L.total);
-  ABD_CHECK((reinterpret_cast<uintptr_t>(ws) & 15) == 0, ABD_E_INVALID, "workspace must be 16-byte aligned");
-  c->ws = static_cast<char*>(ws);
-  c->s = static_cast<hipStream_t>(stream);
-  c->B = B;
-  c->params = params;
-  c->grads = grads;
-  return ABD_OK;
+  return make_ctx(net, B, params, grads, ws, bytes, stream, kGates * 2, make_layout, c);
 }
 
 }  // namespace
@@ -1171,14 +1043,12 @@ size_t abd_lstmattn_workspace_bytes(const abd_lstmattn* net, int64_t batch) {
 int64_t abd_lstmattn_workspace_offset(const abd_lstmattn* net, int64_t batch, const char* name) {
   if (!net || !name || batch < 1) return -1;
   const Layout L = make_layout(net, batch);
-  const struct { const char* n; size_t o; } tab[] = {
+  const NamedOffset tab[] = {
       {"a1", L.a1}, {"a2", L.a2}, {"x0", L.x0}, {"y1", L.y1}, {"gates1", L.gates1}, {"c1", L.c1}, {"y2", L.y2},
       {"gates2", L.gates2}, {"c2", L.c2}, {"dy2", L.dy2}, {"dy1", L.dy1}, {"dx0", L.dx0}, {"q", L.q}, {"att", L.att},
       {"av", L.av}, {"d2", L.d2}, {"d3", L.d3}, {"logits", L.logits}, {"dlogits", L.dlogits}, {"mask", L.mask},
       {"rowinfo", L.rowinfo}};
-  for (const auto& e : tab)
-    if (!strcmp(e.n, name)) return (int64_t)e.o;
-  return -1;
+  return find_offset(tab, name);
 }
 
 int abd_lstmattn_forward(abd_lstmattn* net, const abd_lstmattn_args* a, int train_mode, void* workspace,

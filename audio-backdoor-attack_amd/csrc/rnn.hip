@@ -39,28 +39,12 @@ constexpr int kColsumRows = 512;   // above this many rows the column sums run i
 
 enum { P_FCW = 4 * kLayers, P_FCB, P_COUNT };
 
-#include "reduce_ce.inc"
-
-__device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
+// backward cell, GemmArgs and its three forms, the host helpers; colsum_kernel, ce_kernel, metrics_kernel
+#include "lstm_common.inc"
 
 typedef float f16v __attribute__((ext_vector_type(16)));
 
-// ------------------------------------------------------------------ LDS-tiled fp32 MFMA GEMM
-// C[m][n] (+)= sum_k A(m,k) B(k,n) (+ bias1[n] + bias2[n]); A(m,k) = A[m*sam + k*sak],
-// B(k,n) = B[kb*sbk + n*sbn].  shift != 0: kb = k + shift when k's step (k % T) + shift stays inside
-// [0, T), else the term is zero (h_{t-1} of the recurrent weight gradient).  blockIdx.z takes the
-// k-slice [z*kchunk, (z+1)*kchunk) and writes C + z*cz.
-struct GemmArgs {
-  const float* A;
-  const float* B;
-  float* C;
-  int M, N, K;
-  int64_t sam, sak, sbk, sbn, ldc, cz;
-  const float* bias1;
-  const float* bias2;
-  int accumulate, kchunk, T, shift;
-};
-
+// ------------------------------------------------------------------ LDS-tiled fp32 MFMA GEMM (GemmArgs)
 // An operand tile in LDS: [row][kBK + 1] when k is the contiguous index in memory, [k][rows + 32] when
 // the row is.  Either way consecutive threads write consecutive words, and the MFMA's operand read
 // (lanes 0..31: 32 rows at k, lanes 32..63: the same rows at k + 1) touches 64 different banks.
@@ -257,13 +241,7 @@ __global__ void __launch_bounds__(kT) rnn_gate_bwd_kernel(StepArgs a) {
   float dht = a.dy ? a.dy[row * kHid + u] : 0.0f;
   if (a.dhrec) dht += a.dhrec[e];
   const float dcin = t < T - 1 ? a.dc[e] : 0.0f;
-  const float tc = tanhf(ct);
-  const float dct = dcin + dht * og * (1.0f - tc * tc);
-  gp[0] = dct * gg * ig * (1.0f - ig);
-  gp[kHid] = dct * cp * fg * (1.0f - fg);
-  gp[2 * kHid] = dct * ig * (1.0f - gg * gg);
-  gp[3 * kHid] = dht * tc * og * (1.0f - og);
-  a.dc[e] = dct * fg;
+  lstm_cell_bwd(ig, fg, gg, og, ct, cp, dht, dcin, gp[0], gp[kHid], gp[2 * kHid], gp[3 * kHid], a.dc[e]);
 }
 
 // ------------------------------------------------------------------ host side
@@ -276,12 +254,7 @@ struct Layout {
 
 Layout make_layout(const abd_rnn* n, int64_t B) {
   Layout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t r = o;
-    o += (bytes + 255) & ~(size_t)255;
-    return r;
-  };
+  Take take;
   const size_t BT = (size_t)B * n->T;
   for (int l = 0; l < kLayers; ++l) {
     L.h[l] = take(4 * BT * kHid);
@@ -296,25 +269,18 @@ Layout make_layout(const abd_rnn* n, int64_t B) {
   L.dlogits = take(4 * (size_t)B * n->K);
   L.rowinfo = take(4 * (size_t)B * 4);
   // weight-gradient GEMMs: B*T rows of reduction split into slices of >= kSliceRows rows
-  L.ksplit = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxSlices, (int64_t)BT / kSliceRows));
-  L.kchunk = ((int64_t)BT + L.ksplit - 1) / L.ksplit;
-  L.kchunk = (L.kchunk + kBK - 1) / kBK * kBK;
-  L.ksplit = (int)(((int64_t)BT + L.kchunk - 1) / L.kchunk);
+  const Slices sl = plan_slices((int64_t)BT, kMaxSlices, kSliceRows, kBK);
+  L.ksplit = sl.ksplit;
+  L.kchunk = sl.kchunk;
   L.slab = take(L.ksplit > 1 ? 4 * (size_t)L.ksplit * kGates * kHid : 0);
   L.colp = take(4 * (size_t)64 * kGates);
-  L.total = o;
+  L.total = take.o;
   return L;
 }
 
-struct Ctx {
+struct Ctx : CtxBase {
   const abd_rnn* n;
   Layout L;
-  char* ws;
-  hipStream_t s;
-  int64_t B;
-  const float* params;
-  float* grads;
-  template <class Tp> Tp* at(size_t off) const { return reinterpret_cast<Tp*>(ws + off); }
   const float* p(int i) const { return params + n->off[i]; }
   float* g(int i) const { return grads + n->off[i]; }
 };
@@ -335,49 +301,23 @@ int launch_gemm(hipStream_t s, GemmArgs g, int ksplit = 1) {
   return ABD_OK;
 }
 
-// out[cols] = column sums of A (rows x cols, leading dimension ld); two fixed-order stages past kColsumRows
-int launch_colsum(const Ctx& c, const float* A, int64_t rows, int64_t cols, int64_t ld, float* out) {
-  const int nb = (int)((cols + kRedT - 1) / kRedT);
-  const int S = (cols <= kGates && rows > kColsumRows) ? (int)std::min<int64_t>(64, rows / 256) : 1;
-  if (S <= 1) {
-    colsum_kernel<<<dim3(nb, 1), kRedT, 0, c.s>>>(A, rows, cols, ld, rows, out, 0, 0);
-    ABD_LAUNCH_CHECK();
-    return ABD_OK;
-  }
-  const int64_t chunk = (rows + S - 1) / S;
-  float* part = c.at<float>(c.L.colp);
-  colsum_kernel<<<dim3(nb, S), kRedT, 0, c.s>>>(A, rows, cols, ld, chunk, part, cols, 0);
-  ABD_LAUNCH_CHECK();
-  colsum_kernel<<<dim3(nb, 1), kRedT, 0, c.s>>>(part, S, cols, cols, S, out, 0, 0);
-  ABD_LAUNCH_CHECK();
-  return ABD_OK;
+// out[cols] = column sums of A; two fixed-order stages past kColsumRows rows
+int colsum(const Ctx& c, const float* A, int64_t rows, int64_t cols, int64_t ld, float* out) {
+  return launch_colsum(c, A, rows, cols, ld, out, 0, kGates, kColsumRows);
 }
 
 // dW[j][i] = sum_rows dg[row][j] act[row][i] over all B*T rows, sliced (shift -1: act one step back)
 int weight_grad(const Ctx& c, const float* dg, const float* act, int in, int shift, float* out) {
   const int64_t BT = c.B * c.n->T;
-  GemmArgs g{};
-  g.A = dg;
-  g.B = act;
-  g.M = kGates;
-  g.N = in;
-  g.K = (int)BT;
-  g.sam = 1;
-  g.sak = kGates;
-  g.sbk = in;
-  g.sbn = 1;
-  g.ldc = in;
+  GemmArgs g = gemm_tn(dg, act, in, out, kGates, in, BT);
   g.T = c.n->T;
   g.shift = shift;
-  if (c.L.ksplit <= 1) {
-    g.C = out;
-    return launch_gemm(c.s, g);
-  }
+  if (c.L.ksplit <= 1) return launch_gemm(c.s, g);
   g.C = c.at<float>(c.L.slab);
   g.cz = (int64_t)kGates * in;
   g.kchunk = (int)c.L.kchunk;
   if (int rc = launch_gemm(c.s, g, c.L.ksplit)) return rc;
-  return launch_colsum(c, g.C, c.L.ksplit, g.cz, g.cz, out);
+  return colsum(c, g.C, c.L.ksplit, g.cz, g.cz, out);
 }
 
 int run_forward(const Ctx& c, const float* x) {
@@ -387,18 +327,8 @@ int run_forward(const Ctx& c, const float* x) {
   int width = c.n->F;
   for (int l = 0; l < kLayers; ++l) {
     float* gates = c.at<float>(c.L.gates[l]);
-    GemmArgs g{};   // x W_ih^T + b_ih + b_hh over all B*T rows
-    g.A = in;
-    g.B = c.p(4 * l);
-    g.C = gates;
-    g.M = (int)BT;
-    g.N = kGates;
-    g.K = width;
-    g.sam = width;
-    g.sak = 1;
-    g.sbk = 1;
-    g.sbn = width;
-    g.ldc = kGates;
+    // x W_ih^T + b_ih + b_hh over all B*T rows
+    GemmArgs g = gemm_nt(in, width, c.p(4 * l), gates, (int)BT, kGates, width);
     g.bias1 = c.p(4 * l + 2);
     g.bias2 = c.p(4 * l + 3);
     if (int rc = launch_gemm(c.s, g)) return rc;
@@ -418,76 +348,22 @@ int run_forward(const Ctx& c, const float* x) {
     in = sa.h;
     width = kHid;
   }
-  GemmArgs f{};   // fc on the top layer's last step
-  f.A = c.at<float>(c.L.h[kLayers - 1]) + (int64_t)(T - 1) * kHid;
-  f.B = c.p(P_FCW);
-  f.C = c.at<float>(c.L.logits);
-  f.M = (int)c.B;
-  f.N = c.n->K;
-  f.K = kHid;
-  f.sam = (int64_t)T * kHid;
-  f.sak = 1;
-  f.sbk = 1;
-  f.sbn = kHid;
-  f.ldc = c.n->K;
+  // fc on the top layer's last step
+  GemmArgs f = gemm_nt(c.at<float>(c.L.h[kLayers - 1]) + (int64_t)(T - 1) * kHid, (int64_t)T * kHid, c.p(P_FCW),
+                       c.at<float>(c.L.logits), (int)c.B, c.n->K, kHid);
   f.bias1 = c.p(P_FCB);
   return launch_gemm(c.s, f);
-}
-
-int run_ce(const Ctx& c, const int64_t* labels, const int64_t* ind, bool grad, float grad_scale, float* logits_out,
-           int64_t* metrics) {
-  CeArgs ce{};
-  ce.logits = c.at<float>(c.L.logits);
-  ce.labels = labels;
-  ce.ind = ind;
-  ce.dlogits = grad ? c.at<float>(c.L.dlogits) : nullptr;
-  ce.rowinfo = c.at<float>(c.L.rowinfo);
-  ce.logits_out = logits_out;
-  ce.K = c.n->K;
-  ce.scale = grad_scale / (float)c.B;
-  if (!labels && !logits_out) return ABD_OK;
-  ce_kernel<<<(unsigned)c.B, 64, 0, c.s>>>(ce);
-  ABD_LAUNCH_CHECK();
-  if (labels && metrics) {
-    metrics_kernel<<<1, kRedT, 0, c.s>>>(ce.rowinfo, (int)c.B, metrics, (double)grad_scale);
-    ABD_LAUNCH_CHECK();
-  }
-  return ABD_OK;
 }
 
 int run_backward(const Ctx& c, const float* x, const float* dlogits) {
   const int T = c.n->T, K = c.n->K;
   const int64_t BT = c.B * T;
   const float* hlast = c.at<float>(c.L.h[kLayers - 1]) + (int64_t)(T - 1) * kHid;
-  {
-    GemmArgs g{};   // dfc.weight[j][i] = sum_b dlogits[b][j] h_{T-1}[b][i]
-    g.A = dlogits;
-    g.B = hlast;
-    g.C = c.g(P_FCW);
-    g.M = K;
-    g.N = kHid;
-    g.K = (int)c.B;
-    g.sam = 1;
-    g.sak = K;
-    g.sbk = (int64_t)T * kHid;
-    g.sbn = 1;
-    g.ldc = kHid;
-    if (int rc = launch_gemm(c.s, g)) return rc;
-    if (int rc = launch_colsum(c, dlogits, c.B, K, K, c.g(P_FCB))) return rc;
-    GemmArgs d{};   // dh_{T-1} of the top layer = dlogits fc.weight; its dy is zero everywhere else
-    d.A = dlogits;
-    d.B = c.p(P_FCW);
-    d.C = c.at<float>(c.L.dhtop);
-    d.M = (int)c.B;
-    d.N = kHid;
-    d.K = K;
-    d.sam = K;
-    d.sak = 1;
-    d.sbk = kHid;
-    d.sbn = 1;
-    d.ldc = kHid;
-    if (int rc = launch_gemm(c.s, d)) return rc;
-  }
+  // dfc.weight[j][i] = sum_b dlogits[b][j] h_{T-1}[b][i]
+  if (int rc = launch_gemm(c.s, gemm_tn(dlogits, hlast, (int64_t)T * kHid, c.g(P_FCW), K, kHid, c.B))) return rc;
+  if (int rc = colsum(c, dlogits, c.B, K, K, c.g(P_FCB))) return rc;
+  // dh_{T-1} of the top layer = dlogits fc.weight; its dy is zero everywhere else
+  if (int rc = launch_gemm(c.s, gemm_nn(dlogits, K, c.p(P_FCW), c.at<float>(c.L.dhtop), (int)c.B, kHid, K))) return rc;
   float* dy = c.at<float>(c.L.dy);
   float* dhrec = c.at<float>(c.L.dhrec);
   for (int l = kLayers - 1; l >= 0; --l) {
@@ -503,17 +379,8 @@ int run_backward(const Ctx& c, const float* x, const float* dlogits) {
     sa.dc = c.at<float>(c.L.dc);
     sa.B = (int)c.B;
     sa.T = T;
-    GemmArgs r{};   // dh_{t-1} = dG_t W_hh
-    r.B = c.p(4 * l + 1);
-    r.C = dhrec;
-    r.M = (int)c.B;
-    r.N = kHid;
-    r.K = kGates;
-    r.sam = (int64_t)T * kGates;
-    r.sak = 1;
-    r.sbk = kHid;
-    r.sbn = 1;
-    r.ldc = kHid;
+    // dh_{t-1} = dG_t W_hh; A is set per step
+    GemmArgs r = gemm_nn(nullptr, (int64_t)T * kGates, c.p(4 * l + 1), dhrec, (int)c.B, kHid, kGates);
     const unsigned nblk = (unsigned)((c.B * kHid + kT - 1) / kT);
     for (int t = T - 1; t >= 0; --t) {
       sa.t = t;
@@ -531,22 +398,11 @@ int run_backward(const Ctx& c, const float* x, const float* dlogits) {
     } else {
       ABD_HIP(hipMemsetAsync(c.g(4 * l + 1), 0, sizeof(float) * kGates * kHid, c.s));
     }
-    if (int rc = launch_colsum(c, gates, BT, kGates, kGates, c.g(4 * l + 2))) return rc;
+    if (int rc = colsum(c, gates, BT, kGates, kGates, c.g(4 * l + 2))) return rc;
     ABD_HIP(hipMemcpyAsync(c.g(4 * l + 3), c.g(4 * l + 2), sizeof(float) * kGates, hipMemcpyDeviceToDevice, c.s));
     if (l > 0) {
-      GemmArgs d{};   // gradient of the layer below's output: dG W_ih
-      d.A = gates;
-      d.B = c.p(4 * l);
-      d.C = dy;
-      d.M = (int)BT;
-      d.N = kHid;
-      d.K = kGates;
-      d.sam = kGates;
-      d.sak = 1;
-      d.sbk = kHid;
-      d.sbn = 1;
-      d.ldc = kHid;
-      if (int rc = launch_gemm(c.s, d)) return rc;
+      // gradient of the layer below's output: dG W_ih
+      if (int rc = launch_gemm(c.s, gemm_nn(gates, kGates, c.p(4 * l), dy, (int)BT, kHid, kGates))) return rc;
     }
   }
   return ABD_OK;
@@ -554,20 +410,7 @@ int run_backward(const Ctx& c, const float* x, const float* dlogits) {
 
 int make_ctx(const abd_rnn* net, int64_t B, const float* params, float* grads, void* ws, size_t bytes,
              abd_stream_t stream, Ctx* c) {
-  ABD_CHECK(net != nullptr, ABD_E_INVALID, "NULL network");
-  ABD_CHECK(B >= 1 && B * (int64_t)net->T * kGates < (1LL << 31), ABD_E_INVALID,
-            "batch %lld outside the kernels' 32-bit row range", (long long)B);
-  ABD_CHECK(params != nullptr, ABD_E_INVALID, "NULL params");
-  c->n = net;
-  c->L = make_layout(net, B);
-  ABD_CHECK(ws != nullptr && bytes >= c->L.total, ABD_E_WORKSPACE, "workspace %zu < %zu bytes", bytes, c->L.total);
-  ABD_CHECK((reinterpret_cast<uintptr_t>(ws) & 15) == 0, ABD_E_INVALID, "workspace must be 16-byte aligned");
-  c->ws = static_cast<char*>(ws);
-  c->s = static_cast<hipStream_t>(stream);
-  c->B = B;
-  c->params = params;
-  c->grads = grads;
-  return ABD_OK;
+  return make_ctx(net, B, params, grads, ws, bytes, stream, kGates, make_layout, c);
 }
 
 }  // namespace
@@ -624,13 +467,11 @@ size_t abd_rnn_workspace_bytes(const abd_rnn* net, int64_t batch) {
 int64_t abd_rnn_workspace_offset(const abd_rnn* net, int64_t batch, const char* name) {
   if (!net || !name || batch < 1) return -1;
   const Layout L = make_layout(net, batch);
-  const struct { const char* n; size_t o; } tab[] = {
+  const NamedOffset tab[] = {
       {"h1", L.h[0]}, {"h2", L.h[1]}, {"h3", L.h[2]}, {"c1", L.c[0]}, {"c2", L.c[1]}, {"c3", L.c[2]},
       {"gates1", L.gates[0]}, {"gates2", L.gates[1]}, {"gates3", L.gates[2]}, {"logits", L.logits},
       {"dlogits", L.dlogits}, {"rowinfo", L.rowinfo}};
-  for (const auto& e : tab)
-    if (!strcmp(e.n, name)) return (int64_t)e.o;
-  return -1;
+  return find_offset(tab, name);
 }
 
 int abd_rnn_forward(abd_rnn* net, const abd_rnn_args* a, void* workspace, size_t workspace_bytes,

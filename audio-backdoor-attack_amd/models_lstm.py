@@ -17,7 +17,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import _lib as L
+from . import _flat, _lib as L
 from .models import DROPOUT_SOURCES, draw_dropout_nonce, dropout_seed
 
 _RNN = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
@@ -39,52 +39,22 @@ def tile_rows() -> int:
 
 
 def net_handle(T: int, F: int, K: int):
-    h = C.c_void_p()
-    L.check(L.lib().abd_lstmattn_create(int(T), int(F), int(K), C.byref(h)), "abd_lstmattn_create")
-    return h
+    return _flat.net_handle("abd_lstmattn", T, F, K)
 
 
-class _Engine:
-    """libabd network handle + flat device buffers for one (T, F, K) geometry."""
+class _Engine(_flat.FlatEngine):
+    """The 34 parameters, the 22 running statistics and the two num_batches_tracked counters."""
 
     def __init__(self, model: "lstmwithattention", T: int, F: int, device: torch.device):
-        lib = L.lib()
-        self.T, self.F, self.K = T, F, model.output.out_features
-        self.device = device
-        self.h = net_handle(T, F, self.K)
-        offs = (C.c_int64 * (N_PARAMS + 1))()
-        L.check(lib.abd_lstmattn_param_offsets(self.h, offs), "abd_lstmattn_param_offsets")
-        self.offsets = list(offs)
-        self.n = self.offsets[-1]
-        self.params = torch.empty(self.n, dtype=torch.float32, device=device)
-        self.grads = torch.zeros(self.n, dtype=torch.float32, device=device)
-        self.exp_avg = None
-        self.exp_avg_sq = None
-        self.running = torch.empty(22, dtype=torch.float32, device=device)
-        self.nbt = torch.zeros(2, dtype=torch.int64, device=device)
-        self._ws = None
-        self.token = 0
-        self.last_train_token = -1
-
-    def workspace(self, batch):
-        need = L.lib().abd_lstmattn_workspace_bytes(self.h, int(batch))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
-
-    def views(self, buf):
-        return [buf[self.offsets[i]:self.offsets[i + 1]] for i in range(N_PARAMS)]
-
-    def __del__(self):
-        try:
-            if self.h and self.h.value:
-                L.lib().abd_lstmattn_destroy(self.h)
-        except Exception:
-            pass
+        super().__init__("abd_lstmattn", N_PARAMS, T, F, model.output.out_features, device, running=22, nbt=2)
 
 
-class lstmwithattention(nn.Module):
+class lstmwithattention(_flat.FlatModule, nn.Module):
     """Reference-compatible lstmwithattention whose forward/backward run on libabd (HIP)."""
+
+    PARAM_ORDER, RUNNING_ORDER, ARGS, ENGINE = PARAM_ORDER, RUNNING_ORDER, L.LstmAttnArgs, _Engine
+    BACKWARD_ORDER = ("lstmwithattention backward must directly follow its train-mode forward (activations live in "
+                      "the shared workspace)")
 
     def __init__(self, classes, time_len, seq_len):
         super().__init__()
@@ -146,70 +116,19 @@ class lstmwithattention(nn.Module):
         return st
 
     # ------------------------------------------------------------------ binding
-    def _param_list(self):
-        d = dict(self.named_parameters())
-        return [d[n] for n in PARAM_ORDER]
-
-    def _bound(self, eng) -> bool:
-        if eng is None:
-            return False
-        base = eng.params.data_ptr()
-        for p, off in zip(self._param_list(), eng.offsets):
-            if p.data.data_ptr() != base + 4 * off or p.device != eng.device:
-                return False
-        rbase = eng.running.data_ptr()
-        o = 0
-        for name, c in RUNNING_ORDER:
-            bn = getattr(self, name)
-            if bn.running_mean.data_ptr() != rbase + 4 * o or bn.running_var.data_ptr() != rbase + 4 * (o + c):
-                return False
-            o += 2 * c
-        return True
-
     def engine(self, x: torch.Tensor) -> _Engine:
         """Bind (or re-bind) the parameters to flat device buffers for x's geometry."""
         T, F = int(x.shape[-2]), int(x.shape[-1])
         if T != self.dense2.in_features or F != self.rnn1.input_size:
             raise ValueError(f"input (T, F) = ({T}, {F}) but the model was built for seq_len "
                              f"{self.dense2.in_features}, time_len {self.rnn1.input_size}")
-        eng = self._engine
-        if eng is not None and (eng.T, eng.F) == (T, F) and eng.device == x.device and self._bound(eng):
-            return eng
-        new = _Engine(self, T, F, x.device)
-        if getattr(self, "_dropout_nonce", None) is None:
+        bound = self._engine
+        eng = self._bind(T, F, x.device)
+        if eng is not bound and getattr(self, "_dropout_nonce", None) is None:
             self._dropout_nonce = draw_dropout_nonce(x.device)
-        with torch.no_grad():
-            for p, v in zip(self._param_list(), new.views(new.params)):
-                v.copy_(p.data.reshape(-1))
-                p.data = v.view(p.shape)
-            o = 0
-            for i, (name, c) in enumerate(RUNNING_ORDER):
-                bn = getattr(self, name)
-                new.running[o:o + c].copy_(bn.running_mean)
-                new.running[o + c:o + 2 * c].copy_(bn.running_var)
-                bn.running_mean = new.running[o:o + c]
-                bn.running_var = new.running[o + c:o + 2 * c]
-                new.nbt[i].copy_(bn.num_batches_tracked)
-                bn.num_batches_tracked = new.nbt[i]
-                o += 2 * c
-        # nn.LSTM caches a flattened copy of its weights for the vendor RNN kernels; they are views now
-        for rnn in (self.rnn1, self.rnn2):
-            rnn._flat_weights = [getattr(rnn, n) for n in rnn._flat_weights_names]
-        self._engine = new
-        return new
+        return eng
 
     # ------------------------------------------------------------------ launches
-    def _args(self, eng, x, B):
-        a = L.LstmAttnArgs()
-        a.x = x.data_ptr()
-        a.batch = B
-        a.params = eng.params.data_ptr()
-        a.grads = eng.grads.data_ptr()
-        a.running = eng.running.data_ptr()
-        a.num_batches_tracked = eng.nbt.data_ptr()
-        a.grad_scale = 1.0
-        return a
-
     def _check_input(self, x):
         L.require_device(x, "lstmwithattention input")
         if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
@@ -219,7 +138,7 @@ class lstmwithattention(nn.Module):
         self._check_input(x)
         self.engine(x)
         if self.training and torch.is_grad_enabled():
-            return _LstmAttnFunction.apply(x, self, *self._param_list())
+            return _flat.FlatFunction.apply(x, self, *self._param_list())
         return self.hip_forward(x, train=self.training)
 
     def hip_forward(self, x, train: bool, seed: int | None = None, mask=None, mask_out=None):
@@ -242,39 +161,10 @@ class lstmwithattention(nn.Module):
             a.mask_in = mask.data_ptr()
         if mask_out is not None:
             a.mask_out = mask_out.data_ptr()
-        rc = L.lib().abd_lstmattn_forward(eng.h, C.byref(a), 1, ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
-        L.check(rc, "abd_lstmattn_forward")
+        eng.call("forward", C.byref(a), 1, ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
         eng.token += 1
         eng.last_train_token = eng.token
         return out
 
-    def hip_backward(self, x, dlogits, token):
-        eng = self._engine
-        if eng is None or token != eng.last_train_token:
-            raise L.AbdError("lstmwithattention backward must directly follow its train-mode forward (activations "
-                             "live in the shared workspace)")
-        B = x.shape[0]
-        ws = eng.workspace(B)
-        a = self._args(eng, x, B)
-        dl = dlogits.contiguous()
-        rc = L.lib().abd_lstmattn_backward(eng.h, C.byref(a), dl.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          L.stream_ptr(x.device))
-        L.check(rc, "abd_lstmattn_backward")
-        return eng.views(eng.grads)
-
-
-class _LstmAttnFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        out = model.hip_forward(x, train=True)
-        ctx.model = model
-        ctx.token = model._engine.last_train_token
-        ctx.save_for_backward(x)
-        ctx.shapes = [p.shape for p in params]
-        return out
-
-    @staticmethod
-    def backward(ctx, dl):
-        (x,) = ctx.saved_tensors
-        gs = ctx.model.hip_backward(x, dl, ctx.token)
-        return (None, None, *[g.view(s).clone() for g, s in zip(gs, ctx.shapes)])
+    def hip_train_forward(self, x):
+        return self.hip_forward(x, train=True)

@@ -40,6 +40,7 @@ from torch import Tensor
 
 from . import _lib as L
 from . import features as F
+from ._flat import net_handle
 
 _NETS: dict = {}
 
@@ -748,31 +749,57 @@ def _(x, labels, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracke
     return x.new_empty((x.shape[0], num_classes))
 
 
-# --------------------------------------------------------------------------- lstmwithattention
-_LSTM_NETS: dict = {}
+# --------------------------------------------------------------------------- lstmwithattention, RNN
+_FLAT_NETS: dict = {}
 
 
-def _lstm_net(T: int, F: int, K: int):
-    """A cached libabd lstmwithattention handle for one geometry (shapes only, no device state)."""
-    key = (int(T), int(F), int(K))
-    h = _LSTM_NETS.get(key)
+def _flat_net(prefix: str, T: int, F: int, K: int):
+    """A cached libabd handle (prefix abd_lstmattn / abd_rnn) for one geometry: shapes only, no device state."""
+    key = (prefix, int(T), int(F), int(K))
+    h = _FLAT_NETS.get(key)
     if h is None:
-        h = C.c_void_p()
-        L.check(L.lib().abd_lstmattn_create(key[0], key[1], key[2], C.byref(h)), "abd_lstmattn_create")
-        _LSTM_NETS[key] = h
+        h = _FLAT_NETS[key] = net_handle(*key)
     return h
 
 
-def _lstm_eval(x, params, running, num_classes, labels, indicators, metrics):
-    L.require_device(x, "lstmwithattention input")
+def _flat_begin(prefix, what, x, num_classes):
+    """What every entry point of either model starts from: (name -> lib function, handle, B, the logits to return,
+    the (workspace, bytes, stream) arguments every call ends with)."""
+    L.require_device(x, f"{what} input")
     B, T, F = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    h = _lstm_net(T, F, num_classes)
+    h = _flat_net(prefix, T, F, num_classes)
     out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
-    ws = _ws(L.lib().abd_lstmattn_workspace_bytes(h, B), x.device)
-    L.check(L.lib().abd_lstmattn_eval(h, x.data_ptr(), B, params.data_ptr(), running.data_ptr(), _ptr(labels),
-                                      _ptr(indicators), out.data_ptr(), _ptr(metrics), ws.data_ptr(), ws.numel(),
-                                      L.stream_ptr(x.device)), "abd_lstmattn_eval")
+    ws = _ws(getattr(L.lib(), f"{prefix}_workspace_bytes")(h, B), x.device)
+    return (lambda name: getattr(L.lib(), f"{prefix}_{name}")), h, B, out, (ws.data_ptr(), ws.numel(),
+                                                                         L.stream_ptr(x.device))
+
+
+def _flat_eval(prefix, what, x, params, running, num_classes, labels, indicators, metrics):
+    """The eval entry point of either model; running: (the BatchNorm statistics,), () for a model without any."""
+    fn, h, B, out, tail = _flat_begin(prefix, what, x, num_classes)
+    L.check(fn("eval")(h, x.data_ptr(), B, params.data_ptr(), *[r.data_ptr() for r in running], _ptr(labels),
+                       _ptr(indicators), out.data_ptr(), _ptr(metrics), *tail), f"{prefix}_eval")
     return out
+
+
+def _flat_train_step(prefix, what, a, x, labels, indicators, params, grads, exp_avg, exp_avg_sq, metrics, num_classes,
+                     adam_step, lr, beta1, beta2, eps):
+    """The fused step of either model: fills the fields both args structs share into a (the caller set the rest)."""
+    fn, h, B, out, tail = _flat_begin(prefix, what, x, num_classes)
+    a.x, a.batch = x.data_ptr(), B
+    a.labels, a.indicators = labels.data_ptr(), _ptr(indicators)
+    a.params, a.grads = params.data_ptr(), grads.data_ptr()
+    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    a.lr, a.beta1, a.beta2, a.eps = float(lr), float(beta1), float(beta2), float(eps)
+    a.adam_step, a.do_update = int(adam_step), 1 if adam_step > 0 else 0
+    a.logits_out, a.metrics, a.grad_scale = out.data_ptr(), metrics.data_ptr(), 1.0
+    L.check(fn("train_step")(h, C.byref(a), *tail), f"{prefix}_train_step")
+    return out
+
+
+def _lstm_eval(x, params, running, num_classes, labels, indicators, metrics):
+    return _flat_eval("abd_lstmattn", "lstmwithattention", x, params, (running,), num_classes, labels, indicators,
+                      metrics)
 
 
 @torch.library.custom_op("abd::lstmattn_eval", mutates_args=())
@@ -809,25 +836,12 @@ def lstmattn_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor],
                         eps: float, seed: int, counter: int, mask: Optional[Tensor] = None) -> Tensor:
     """One fused train() iteration of lstmwithattention on the device; returns the batch's logits (B, K).
     adam_step >= 1 applies torch.optim.Adam (that step index); 0 leaves params untouched."""
-    L.require_device(x, "lstmwithattention input")
-    B, T, F = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    h = _lstm_net(T, F, num_classes)
-    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
     a = L.LstmAttnArgs()
-    a.x, a.batch = x.data_ptr(), B
-    a.labels, a.indicators = labels.data_ptr(), _ptr(indicators)
-    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
-    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
-    a.num_batches_tracked = num_batches_tracked.data_ptr()
-    a.lr, a.beta1, a.beta2, a.eps = float(lr), float(beta1), float(beta2), float(eps)
-    a.adam_step, a.do_update = int(adam_step), 1 if adam_step > 0 else 0
+    a.running, a.num_batches_tracked = running.data_ptr(), num_batches_tracked.data_ptr()
     a.seed, a.counter = int(seed), int(counter)
     a.mask_in = _ptr(mask)
-    a.logits_out, a.metrics, a.grad_scale = out.data_ptr(), metrics.data_ptr(), 1.0
-    ws = _ws(L.lib().abd_lstmattn_workspace_bytes(h, B), x.device)
-    L.check(L.lib().abd_lstmattn_train_step(h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
-            "abd_lstmattn_train_step")
-    return out
+    return _flat_train_step("abd_lstmattn", "lstmwithattention", a, x, labels, indicators, params, grads, exp_avg,
+                            exp_avg_sq, metrics, num_classes, adam_step, lr, beta1, beta2, eps)
 
 
 @lstmattn_train_step.register_fake
@@ -836,31 +850,8 @@ def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, running, num_ba
     return x.new_empty((x.shape[0], num_classes))
 
 
-# --------------------------------------------------------------------------- RNN
-_RNN_NETS: dict = {}
-
-
-def _rnn_net(T: int, F: int, K: int):
-    """A cached libabd RNN handle for one geometry (shapes only, no device state)."""
-    key = (int(T), int(F), int(K))
-    h = _RNN_NETS.get(key)
-    if h is None:
-        h = C.c_void_p()
-        L.check(L.lib().abd_rnn_create(key[0], key[1], key[2], C.byref(h)), "abd_rnn_create")
-        _RNN_NETS[key] = h
-    return h
-
-
 def _rnn_eval(x, params, num_classes, labels, indicators, metrics):
-    L.require_device(x, "RNN input")
-    B, T, F = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    h = _rnn_net(T, F, num_classes)
-    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
-    ws = _ws(L.lib().abd_rnn_workspace_bytes(h, B), x.device)
-    L.check(L.lib().abd_rnn_eval(h, x.data_ptr(), B, params.data_ptr(), _ptr(labels), _ptr(indicators),
-                                 out.data_ptr(), _ptr(metrics), ws.data_ptr(), ws.numel(),
-                                 L.stream_ptr(x.device)), "abd_rnn_eval")
-    return out
+    return _flat_eval("abd_rnn", "RNN", x, params, (), num_classes, labels, indicators, metrics)
 
 
 @torch.library.custom_op("abd::rnn_eval", mutates_args=())
@@ -893,22 +884,8 @@ def rnn_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor], para
                    lr: float, beta1: float, beta2: float, eps: float) -> Tensor:
     """One fused train() iteration of RNN on the device; returns the batch's logits (B, K).
     adam_step >= 1 applies torch.optim.Adam (that step index); 0 leaves params untouched."""
-    L.require_device(x, "RNN input")
-    B, T, F = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    h = _rnn_net(T, F, num_classes)
-    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
-    a = L.RnnArgs()
-    a.x, a.batch = x.data_ptr(), B
-    a.labels, a.indicators = labels.data_ptr(), _ptr(indicators)
-    a.params, a.grads = params.data_ptr(), grads.data_ptr()
-    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
-    a.lr, a.beta1, a.beta2, a.eps = float(lr), float(beta1), float(beta2), float(eps)
-    a.adam_step, a.do_update = int(adam_step), 1 if adam_step > 0 else 0
-    a.logits_out, a.metrics, a.grad_scale = out.data_ptr(), metrics.data_ptr(), 1.0
-    ws = _ws(L.lib().abd_rnn_workspace_bytes(h, B), x.device)
-    L.check(L.lib().abd_rnn_train_step(h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
-            "abd_rnn_train_step")
-    return out
+    return _flat_train_step("abd_rnn", "RNN", L.RnnArgs(), x, labels, indicators, params, grads, exp_avg, exp_avg_sq,
+                            metrics, num_classes, adam_step, lr, beta1, beta2, eps)
 
 
 @rnn_train_step.register_fake

@@ -201,13 +201,10 @@ def train_step(model: smallcnn, x, labels, indicators, adam: AdamBinding | None,
     return a
 
 
-def lstm_train_step(model: lstmwithattention, x, labels, indicators, adam: AdamBinding | None,
-                    metrics: torch.Tensor | None, mask=None, mask_out=None, do_update=True, grad_scale=1.0, seed=None,
-                    logits_out=None):
-    """One fused device step of lstmwithattention (forward + CE + backward [+ Adam]) through the C ABI."""
+def _flat_step_args(model, x, labels, indicators, adam, metrics, do_update, grad_scale, logits_out):
+    """(engine, args struct) of a fused lstmwithattention / RNN step: everything the two steps share."""
     eng = model.engine(x)
-    B = x.shape[0]
-    a = model._args(eng, x, B)
+    a = model._args(eng, x, x.shape[0])
     a.labels = labels.data_ptr() if labels is not None else None
     a.indicators = indicators.data_ptr() if indicators is not None else None
     if adam is not None:
@@ -217,52 +214,44 @@ def lstm_train_step(model: lstmwithattention, x, labels, indicators, adam: AdamB
             adam.step += 1
             a.adam_step = adam.step
             a.do_update = 1
-    a.seed = dropout_seed(x.device, model) if seed is None else seed
-    a.counter = model._step
-    model._step += 1
-    if mask is None:
-        mask = model.step_mask(B, x.device)
-    if mask is not None:
-        a.mask_in = mask.data_ptr()
-    if mask_out is not None:
-        a.mask_out = mask_out.data_ptr()
     if metrics is not None:
         a.metrics = metrics.data_ptr()
     if logits_out is not None:
         a.logits_out = logits_out.data_ptr()
     a.grad_scale = float(grad_scale)
-    ws = eng.workspace(B)
-    rc = L.lib().abd_lstmattn_train_step(eng.h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
-    L.check(rc, "abd_lstmattn_train_step")
+    return eng, a
+
+
+def _flat_step(eng, a, x):
+    ws = eng.workspace(x.shape[0])
+    eng.call("train_step", C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
     return a
+
+
+def lstm_train_step(model: lstmwithattention, x, labels, indicators, adam: AdamBinding | None,
+                    metrics: torch.Tensor | None, mask=None, mask_out=None, do_update=True, grad_scale=1.0, seed=None,
+                    logits_out=None):
+    """One fused device step of lstmwithattention (forward + CE + backward [+ Adam]) through the C ABI."""
+    eng, a = _flat_step_args(model, x, labels, indicators, adam, metrics, do_update, grad_scale, logits_out)
+    a.seed = dropout_seed(x.device, model) if seed is None else seed
+    a.counter = model._step
+    model._step += 1
+    if mask is None:
+        mask = model.step_mask(x.shape[0], x.device)
+    if mask is not None:
+        a.mask_in = mask.data_ptr()
+    if mask_out is not None:
+        a.mask_out = mask_out.data_ptr()
+    return _flat_step(eng, a, x)
 
 
 def rnn_train_step(model: RNN, x, labels, indicators, adam: AdamBinding | None, metrics: torch.Tensor | None,
                    do_update=True, grad_scale=1.0, logits_out=None):
     """One fused device step of RNN (forward + CE + backward [+ Adam]) through the C ABI."""
     x = model._prepare(x)
-    eng = model.engine(x)
-    B = x.shape[0]
-    a = model._args(eng, x, B)
-    a.labels = labels.data_ptr() if labels is not None else None
-    a.indicators = indicators.data_ptr() if indicators is not None else None
-    if adam is not None:
-        a.exp_avg, a.exp_avg_sq = eng.exp_avg.data_ptr(), eng.exp_avg_sq.data_ptr()
-        a.lr, (a.beta1, a.beta2), a.eps = adam.lr, adam.betas, adam.eps
-        if do_update:
-            adam.step += 1
-            a.adam_step = adam.step
-            a.do_update = 1
-    if metrics is not None:
-        a.metrics = metrics.data_ptr()
-    if logits_out is not None:
-        a.logits_out = logits_out.data_ptr()
-    a.grad_scale = float(grad_scale)
-    ws = eng.workspace(B)
+    eng, a = _flat_step_args(model, x, labels, indicators, adam, metrics, do_update, grad_scale, logits_out)
     eng.last_train_token = -1   # the step consumes the workspace a pending autograd backward would read
-    rc = L.lib().abd_rnn_train_step(eng.h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
-    L.check(rc, "abd_rnn_train_step")
-    return a
+    return _flat_step(eng, a, x)
 
 
 def op_train_step(model: smallcnn | lstmwithattention, x, labels, indicators, adam: AdamBinding,
