@@ -458,14 +458,10 @@ __device__ __forceinline__ void grad_tile(const float* __restrict__ A, int lda, 
   }
 }
 
-#ifndef ABD_HEAD_ABL  // measurement builds (results discarded): 1 no fc1 weight-gradient tiles, 2 no BN3 apply
-#define ABD_HEAD_ABL 0
-#endif
 __global__ void __launch_bounds__(kT) head_bwd_kernel(HeadArgs a) {
   const int tid = threadIdx.x;
   int bid = blockIdx.x;
   if (bid < a.n_w1) {  // ---- fc1 weight gradient: dW1[u][f] = sum_b da[b][u] p3d[b][f]
-    if constexpr ((ABD_HEAD_ABL & 1) != 0) return;
     grad_tile(a.da, 128, 128, a.p3d, a.F, a.F, a.B, 32 * (bid & 3), 32 * (bid >> 2), a.g_f1w, a.F);
     return;
   }
@@ -516,7 +512,6 @@ __global__ void __launch_bounds__(kT) head_bwd_kernel(HeadArgs a) {
     return;
   }
   bid -= 1;
-  if constexpr ((ABD_HEAD_ABL & 2) != 0) return;
   // ---- BN3 backward applied: dz3 = relu'(r3) * bn_dx(dy routed to the pool argmax) (bn_bwd_apply_kernel)
   // kHeadIT windows per thread; their r3 / dp3 loads are issued before the block reduces the BN3
   // partials, so the reduction's latency overlaps them

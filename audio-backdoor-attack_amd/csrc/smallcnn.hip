@@ -176,9 +176,6 @@ struct BCoef {
   double g, A, B, pad;
 };
 
-#ifndef ABD_C1_DD
-#define ABD_C1_DD 0
-#endif
 #ifndef ABD_C1W_U
 #define ABD_C1W_U 4  // pool windows per thread whose gradient loads conv1_wgrad_kernel batches
 #endif
@@ -191,8 +188,7 @@ __device__ __forceinline__ float bn_dx(float dy, float r, float4 /*cf*/, const B
 // The batch-mean terms keep their double precision (no systematic bias for the cancelling
 // weight-gradient sums); what remains is the per-element fp32 rounding the double path also has
 // at its final store.  Channel pairs as float2 vector FMAs (conv1_wgrad_kernel; the library is built
-// without packed FP32, Makefile PKFLAGS, so each is two v_fma_f32); ABD_C1_DD=1 builds the
-// double-precision evaluation instead.
+// without packed FP32, Makefile PKFLAGS, so each is two v_fma_f32).
 struct BCoefF {
   float gh, gl, Ah, Al, Bh, Bl;
 };
@@ -661,7 +657,6 @@ __global__ void __launch_bounds__(kT, ABD_C1W_OCC) conv1_wgrad_kernel(C1Args a) 
     bb[q] = cf.w;
     bc[q] = a.bcoef[c0 + q];
   }
-#if !ABD_C1_DD
   c1f2 fgh, fgl, fAh, fAl, fBh, fBl;  // float-float coefficients of the channel pair
   {
     const BCoefF f0 = bcoef_ff(bc[0]), f1 = bcoef_ff(bc[1]);
@@ -672,7 +667,6 @@ __global__ void __launch_bounds__(kT, ABD_C1W_OCC) conv1_wgrad_kernel(C1Args a) 
     fBh = c1f2{f0.Bh, f1.Bh};
     fBl = c1f2{f0.Bl, f1.Bl};
   }
-#endif
   const int NW = (a.g.W1 + 2) / 3;  // windows incl. a partial trailing one (dy = 0 there)
   static_assert(CPT == 2, "one packed channel pair per thread");
   c1f2 kp[5], vp[5];
@@ -744,10 +738,6 @@ __global__ void __launch_bounds__(kT, ABD_C1W_OCC) conv1_wgrad_kernel(C1Args a) 
       for (int j = 0; j < 3; ++j) {
         if (j >= nw) continue;
         c1f2 dz;
-#if ABD_C1_DD
-        dz.x = r[0][j] > 0.0f ? bn_dx(j == jm[0] ? dd[0] : 0.0f, r[0][j], float4{}, bc[0]) : 0.0f;
-        dz.y = r[1][j] > 0.0f ? bn_dx(j == jm[1] ? dd[1] : 0.0f, r[1][j], float4{}, bc[1]) : 0.0f;
-#else
         {
           const c1f2 dy = c1f2{j == jm[0] ? dd[0] : 0.0f, j == jm[1] ? dd[1] : 0.0f};
           const c1f2 rr = c1f2{r[0][j], r[1][j]};
@@ -757,7 +747,6 @@ __global__ void __launch_bounds__(kT, ABD_C1W_OCC) conv1_wgrad_kernel(C1Args a) 
           dz.x = rr.x > 0.0f ? v.x : 0.0f;
           dz.y = rr.y > 0.0f ? v.y : 0.0f;
         }
-#endif
         vp[0] = __builtin_elementwise_fma(dz, c1f2{xv[0][j], xv[0][j]}, vp[0]);
         vp[1] = __builtin_elementwise_fma(dz, c1f2{xv[0][j + 1], xv[0][j + 1]}, vp[1]);
         vp[2] = __builtin_elementwise_fma(dz, c1f2{xv[1][j], xv[1][j]}, vp[2]);
@@ -1581,9 +1570,6 @@ constexpr int kBM = 128, kKC = 32;
 #ifndef ABD_NT_MINW
 #define ABD_NT_MINW 1
 #endif
-#ifndef ABD_NT_DEBUG
-#define ABD_NT_DEBUG 0
-#endif
 template <int NB, int EPI, int MI = 1, int KC = kKC>
 __global__ void __launch_bounds__(kT, ABD_NT_MINW) gemm_nt_kernel(NTArgs a) {
   // KC-deep K chunks: QPR float4 per staged row, RP rows per pass of the block
@@ -1668,11 +1654,7 @@ __global__ void __launch_bounds__(kT, ABD_NT_MINW) gemm_nt_kernel(NTArgs a) {
       d[3] = rbv[j].w;
     }
     __syncthreads();
-#if ABD_NT_DEBUG == 1  // experiment: operands loaded once per tile (measures MFMA + LDS)
-    if (ch == ch_begin && ch + 1 < nch) load(ch + 1);
-#else
     if (ch + 1 < nch) load(ch + 1);
-#endif
     const float* ap = As + (wave * 32 * MI + (lane & 31)) * LDA + (lane >> 5);
     const float* bp = Bs + (lane & 31) * LDA + (lane >> 5);
 #pragma unroll
@@ -1684,13 +1666,7 @@ __global__ void __launch_bounds__(kT, ABD_NT_MINW) gemm_nt_kernel(NTArgs a) {
       for (int j = 0; j < NJ; ++j) {
         const float bv = bp[j * 32 * LDA + kk];
 #pragma unroll
-        for (int i = 0; i < MI; ++i) {
-#if ABD_NT_DEBUG == 2  // experiment: no MFMA (measures the load / LDS / barrier skeleton)
-          acc[i][j][0] += av[i] * bv;
-#else
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv, acc[i][j], 0, 0, 0);
-#endif
-        }
+        for (int i = 0; i < MI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv, acc[i][j], 0, 0, 0);
       }
     }
     __syncthreads();
@@ -2074,36 +2050,29 @@ __global__ void __launch_bounds__(WPB * 64, 1) conv_ws_split_kernel(NTArgs a) {
   }
 }
 
-// Weight-stationary conv2 FORWARD with the A operand staged through LDS by DMA (ABD_WS_DMA=1,
-// A/B knob).  Same product, tiles, epilogue and summation order as conv_ws_split_kernel<EPI_CONV,
-// 2, 64, 1, .., KO = true>; only how the A fragments reach the registers differs.  The direct path
-// loads each lane's 32 B of its own output row from global memory: the four lanes of a quad (the
-// unit the texture address stage processes together) touch four NHWC rows 256 B apart -- four L1
-// lines per quad, ~58 tag lookups per 1-KB load, TA stalled on the L1 in 35 % of the kernel's
-// cycles.  Here, per 16-channel group, a wave DMAs the tile's whole source span (the 32 output
-// rows' positions plus the taps' +1 / +Ws / +Ws+1 shifts: <= 64 positions x 64 B) into its own
-// LDS buffer with `buffer_load_dwordx4 ... lds`, four lanes per position -- one line per quad --
-// and the four taps read their fragments from it (2 ds_read_b128 per lane and tap; the 16-B chunk
-// is XOR-swizzled by (position >> 2) & 3 so the 16 lanes of a read phase hit distinct banks).
-// Forward taps only ((0,0),(0,1),(1,0),(1,1) with Hs = Ho + 1, Ws = Wo + 1: every tap inside the
-// source), checked by the launcher.  No block barrier in the loop: each wave waits for its own DMA.
-#ifndef ABD_DMA_TRIM
-#define ABD_DMA_TRIM 1
-#endif
+// bf16's weight-stationary conv2 / conv3 GEMMs WITHOUT plane operands (the A source is fp32,
+// NTArgs::src), A staged through LDS by DMA: the forwards by default, the data gradients too under
+// ABD_WS_DMA=2 (ws_kind).  Same product, tiles, epilogue and summation order as
+// conv_ws_split_kernel<EPI, NJ, 64, 1, .., NP = 1>; only how the A fragments reach the registers
+// differs.  The direct path loads each lane's 32 B of its own output row from global memory: the
+// four lanes of a quad (the unit the texture address stage processes together) touch four NHWC
+// rows 256 B apart -- four L1 lines per quad, ~58 tag lookups per 1-KB load, TA stalled on the L1
+// in 35 % of the kernel's cycles.  Here, per 16-channel group, a wave DMAs the tile's source span
+// (the 32 output rows' positions plus the taps' shifts: <= 64 positions x 64 B, and of those only
+// the 16-position blocks the rows' taps reach) into its own LDS buffer with
+// `buffer_load_dwordx4 ... lds`, four lanes per position -- one line per quad -- and the four taps
+// read their fragments from it (2 ds_read_b128 per lane and tap; the 16-B chunk is XOR-swizzled by
+// (position >> 2) & 3 so the 16 lanes of a read phase hit distinct banks), rounding them to bf16
+// for the single MFMA term.  The launcher checks the taps: the forward's ((0,0),(0,1),(1,0),(1,1)
+// with Hs = Ho + 1, Ws = Wo + 1: every tap inside the source) or the data gradient's (masked at the
+// source grid's edges).  No block barrier in the loop: each wave waits for its own DMA.
+// f32split and bf16's plane operands, which this kernel also served once, run on
+// conv_ws_spec_kernel; those instantiations are gone.
 constexpr int kDmaSpan = 64;  // staged positions per tile and group (span <= 31 + 3 + 14 + Ws + 1)
-#ifndef ABD_DMA_ABL  // ablation bits (measurement builds only; results wrong): 1 no epilogue stores,
-#define ABD_DMA_ABL 0  // 2 no DMA waits, 4 no DMA, 8 no A split
-#endif
-// PA (bf16 mode's plane operands, NP = 1): the A source is the producer's bf16 plane (NTArgs::srcs,
-// store_planes4), staged as 32 B per position and group (two lanes per position, 32 positions per
-// DMA instruction: half the instructions and bytes of the fp32 staging), the 16-B half a lane reads
-// XOR-swizzled by (position >> 3) & 1, and read straight into the MFMA operand (no split).
-template <int EPI, int NP, int NJ = 2, bool PA = false>
+template <int EPI, int NJ = 2>
 __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
-  static_assert(!PA || NP == 1, "pre-split staging: the single bf16 plane");
   constexpr int CS = 64, N = 32 * NJ, K = 4 * CS, LD = K + 8, WPB = 8, G = CS / 16;
-  constexpr int PPI = PA ? 32 : 16;  // staged positions per DMA instruction
-  __shared__ __attribute__((aligned(16))) __bf16 Bs[NP][N * LD];
+  __shared__ __attribute__((aligned(16))) __bf16 Bs[N * LD];
   __shared__ __attribute__((aligned(16))) float stage[WPB][kDmaSpan * 16];
   __shared__ float red[WPB][N][2];
   __shared__ float bfold[N];
@@ -2112,10 +2081,9 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
     const int n = idx / (K / 8), k8 = (idx % (K / 8)) * 8;
     const float4 lo = *reinterpret_cast<const float4*>(a.Bw + (int64_t)n * a.ldb + k8);
     const float4 hi = *reinterpret_cast<const float4*>(a.Bw + (int64_t)n * a.ldb + k8 + 4);
-    bf16x8 pl[NP];
-    planes_x8<NP>(lo, hi, pl);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) *reinterpret_cast<bf16x8*>(&Bs[q][n * LD + k8]) = pl[q];
+    bf16x8 pl;
+    round1_x8(lo, hi, &pl);
+    *reinterpret_cast<bf16x8*>(&Bs[n * LD + k8]) = pl;
   }
   if (EPI == EPI_CONV && a.fold_t != nullptr) {
     for (int q = tid; q < N * 8; q += WPB * 64) {
@@ -2142,11 +2110,8 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
     tmin = min(tmin, tofs[t]);
     tmax = max(tmax, tofs[t]);
   }
-  const __amdgpu_buffer_rsrc_t arsrc =
-      PA ? __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.srcs), 0,
-                                             (int)std::min<int64_t>((int64_t)npos * CS * 2, 0x7ffffff0), 0x00020000)
-         : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.src), 0,
-                                             (int)std::min<int64_t>((int64_t)npos * CS * 4, 0x7ffffff0), 0x00020000);
+  const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(a.src), 0, (int)std::min<int64_t>((int64_t)npos * CS * 4, 0x7ffffff0), 0x00020000);
   const int kq = 8 * (lane >> 5);
   float st[NJ][2];
   float bias[NJ];
@@ -2163,24 +2128,16 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
   // position 16 i + l / 4, LDS slot l % 4 holds global chunk (l % 4) ^ ((pos >> 2) & 3)
   // only the 16-position blocks the tile reads (need: wave-uniform; typically 48 of the 64 slots)
   auto dma1 = [&](int p0, int cg, int need, int i) {
-    if (ABD_DMA_ABL & 4) return;
-    if (i > 0 && PPI * i >= need) return;
-    uint32_t off;
-    if constexpr (PA) {  // PA: instruction i, lane l -> position 32 i + l / 2, half (l % 2) ^ ((pos >> 3) & 1)
-      const int pos = 32 * i + (lane >> 1);
-      const int half = (lane & 1) ^ ((pos >> 3) & 1);
-      off = (uint32_t)(((p0 + pos) * CS + cg * 16 + half * 8) * 2);
-    } else {
-      const int pos = 16 * i + (lane >> 2);
-      const int chunk = (lane & 3) ^ ((pos >> 2) & 3);
-      off = (uint32_t)(((p0 + pos) * CS + cg * 16 + chunk * 4) * 4);  // past the end: zeros
-    }
+    if (i > 0 && 16 * i >= need) return;
+    const int pos = 16 * i + (lane >> 2);
+    const int chunk = (lane & 3) ^ ((pos >> 2) & 3);
+    const uint32_t off = (uint32_t)(((p0 + pos) * CS + cg * 16 + chunk * 4) * 4);  // past the end: zeros
     __builtin_amdgcn_raw_ptr_buffer_load_lds(arsrc, (__attribute__((address_space(3))) void*)(sw + i * 256), 16,
                                              (int)off, 0, 0, 0);
   };
   auto dma = [&](int p0, int cg, int need) {
 #pragma unroll
-    for (int i = 0; i < kDmaSpan / PPI; ++i) dma1(p0, cg, need, i);
+    for (int i = 0; i < kDmaSpan / 16; ++i) dma1(p0, cg, need, i);
   };
   const int ntiles = (r_hi - r_lo + 31) / 32;
   const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -2205,7 +2162,7 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
   };
   // first staged position of the tile starting at m: the rows' minimum source index (a source
   // image boundary can step it back) plus the most negative tap
-  // and the number of staged positions its rows' taps reach (ABD_DMA_TRIM=0: always kDmaSpan)
+  // and the number of staged positions its rows' taps reach
   auto span_base = [&](int m, int& need) {
     const int s0 = src_of(min(m + (lane & 31), r_hi - 1));
     int v = s0, u = s0;
@@ -2215,17 +2172,15 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
       u = max(u, __shfl_xor(u, o, 64));
     }
     const int base = __builtin_amdgcn_readfirstlane(v) + tmin;
-    need = ABD_DMA_TRIM ? __builtin_amdgcn_readfirstlane(u) + tmax + 1 - base : kDmaSpan;
+    need = __builtin_amdgcn_readfirstlane(u) + tmax + 1 - base;
     return base;
   };
   // B fragments of step (cg, t), double-buffered one step ahead (the LDS latency off the MFMA path)
-  bf16x8 bvs[2][NJ][NP];
-  auto load_b = [&](int cg, int t, bf16x8 (&bv)[NJ][NP]) {
+  bf16x8 bvs[2][NJ];
+  auto load_b = [&](int cg, int t, bf16x8 (&bv)[NJ]) {
     const int kb = t * CS + cg * 16 + kq;  // KO order: step = cg * 4 + t
 #pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int q = 0; q < NP; ++q) bv[j][q] = *reinterpret_cast<const bf16x8*>(&Bs[q][(32 * j + (lane & 31)) * LD + kb]);
+    for (int j = 0; j < NJ; ++j) bv[j] = *reinterpret_cast<const bf16x8*>(&Bs[(32 * j + (lane & 31)) * LD + kb]);
   };
   int need = kDmaSpan, needn = kDmaSpan;
   int p0 = ntiles > 0 ? span_base(r_lo, need) : 0;
@@ -2251,8 +2206,7 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
       // order).  The count must equal the stores per tile exactly: a larger one lets the DMA
       // of group 0 still be in flight (NJ = 1 issues 16 stores: vmcnt(32) would never wait).
       static_assert(NJ == 1 || NJ == 2, "epilogue store count per tile is 16 * NJ");
-      if (ABD_DMA_ABL & 6) {
-      } else if (cg == 0 && tile > 0) {
+      if (cg == 0 && tile > 0) {
         if constexpr (NJ == 2) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
       } else {
@@ -2262,15 +2216,10 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const int pos = min(max(prow + tofs[t], 0), kDmaSpan - 1);  // an invalid tap's position is clamped
-        if constexpr (PA) {
-          const char* rowp = reinterpret_cast<const char*>(sw) + pos * 32;
-          raw[t][0] = raw[t][1] = *reinterpret_cast<const uint4*>(rowp + (((lane >> 5) ^ ((pos >> 3) & 1)) * 16));
-        } else {
-          const int sx = (pos >> 2) & 3;
-          const float* rowp = sw + pos * 16;
-          raw[t][0] = *reinterpret_cast<const uint4*>(rowp + (((2 * (lane >> 5)) ^ sx) * 4));
-          raw[t][1] = *reinterpret_cast<const uint4*>(rowp + (((2 * (lane >> 5) + 1) ^ sx) * 4));
-        }
+        const int sx = (pos >> 2) & 3;
+        const float* rowp = sw + pos * 16;
+        raw[t][0] = *reinterpret_cast<const uint4*>(rowp + (((2 * (lane >> 5)) ^ sx) * 4));
+        raw[t][1] = *reinterpret_cast<const uint4*>(rowp + (((2 * (lane >> 5) + 1) ^ sx) * 4));
         if constexpr (EPI != EPI_CONV) {  // and zeroed (forward taps never leave the grid)
           if (!((tm >> t) & 1u)) raw[t][0] = raw[t][1] = make_uint4(0u, 0u, 0u, 0u);
         }
@@ -2290,21 +2239,11 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
         const int s = cg * 4 + t;
         // next step's B fragments (past the tile's last step: the next tile's first)
         load_b(((s + 1) % (4 * G)) / 4, (s + 1) % 4, bvs[(s + 1) & 1]);
-        bf16x8 av[NP];
-        if constexpr (PA) {
-          av[0] = __builtin_bit_cast(bf16x8, raw[t][0]);
-        } else if (ABD_DMA_ABL & 8) {
+        bf16x8 av;
+        round1_x8(__builtin_bit_cast(float4, raw[t][0]), __builtin_bit_cast(float4, raw[t][1]), &av);
+        bf16x8 (&bv)[NJ] = bvs[s & 1];
 #pragma unroll
-          for (int q = 0; q < NP; ++q) av[q] = __builtin_bit_cast(bf16x8, q == 1 ? raw[t][1] : raw[t][0]);
-        } else {
-          planes_x8<NP>(__builtin_bit_cast(float4, raw[t][0]), __builtin_bit_cast(float4, raw[t][1]), av);
-        }
-        bf16x8 (&bv)[NJ][NP] = bvs[s & 1];
-#pragma unroll
-        for (int term = 0; term < Terms<NP>::n; ++term)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[Terms<NP>::A[term]], bv[j][Terms<NP>::B[term]], acc[j], 0, 0, 0);
+        for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv[j], acc[j], 0, 0, 0);
       }
     }
     p0 = p0n;
@@ -2323,7 +2262,6 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
           st[j][0] += vs;
           st[j][1] = fmaf(vs, vs, st[j][1]);
         }
-        if ((ABD_DMA_ABL & 1) && __builtin_bit_cast(uint32_t, v) != 0x7fc00001u) continue;
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), orsrc, (int)(ob + 128u * j), 0, 0);
       }
     }
@@ -2350,344 +2288,39 @@ __global__ void __launch_bounds__(512, 1) conv_ws_dma_kernel(NTArgs a) {
   }
 }
 
-// Weight-stationary conv2 GEMM in f32split with the A operand staged PRE-SPLIT (round 4).
-// conv_ws_dma_kernel<EPI, 3> splits every (row, tap) fragment of a 16-channel group after reading it
-// from its fp32 stage -- 32 rows x 4 taps of splits for ~48 distinct positions, 2.7x redundant --
-// and its LDS-DMA pieces cost 60-185 issue cycles each beside MFMAs (MI355X_MICROARCH.md); with the
-// split's VALU they crowd the issue slots the MFMAs need (forward ablation: no DMA issue 0.131 ->
-// 0.083 ms, no split -> 0.106).  Here each wave loads the group's span with plain buffer loads one
-// group ahead (units of 8 channels x 1 position, 32 B, <= 2 per lane), splits each unit ONCE into the
-// three exact bf16 planes, writes them to its own LDS stage (kPreRow = 56 bf16 = 112 B per position:
-// 3 planes x 32 B + 16 B pad, 7 bank groups apart, so 16 consecutive positions hit 16 distinct
-// groups), and the taps read the planes straight into the MFMA operands (3 ds_read_b128 per tap).
-// Same tiles, K order, products, summation order and epilogue as conv_ws_dma_kernel<EPI, 3>.
-// LDS: 101,376 (weights) + 57,344 (stages; the data gradient's 58,240 with a zero position per
-// wave) + 256 = 158,976 / 159,872 B of the CU's 163,840 (the statistics' per-wave partials reuse
-// each wave's stage after its last tile).
-// Ablations (-DABD_PRE_ABL, results discarded; forward / data gradient, ms): 0.121 / 0.123 base; no
-// stage writes 0.099 / 0.093; no split 0.103 / 0.100; no loads 0.112 / 0.114; no output stores
-// 0.117 / 0.110; no MFMAs 0.093 / 0.088 -- the MFMAs are not what bounds it.
-constexpr int kPreRow = 56;
-#ifndef ABD_PRE_ABL  // measurement builds (results discarded): 1 no stage writes, 2 no loads, 4 no MFMAs,
-#define ABD_PRE_ABL 0  // 8 no output stores, 16 no split (raw bits written to the planes)
-#endif
-#ifndef ABD_WS_PRE  // measurement builds: 0 conv_ws_dma_kernel<EPI, 3> everywhere, 1 the conv2 forward,
-#define ABD_WS_PRE 3  // 2 + the conv2 data gradient (default ABD_WS_DMA=1 too), 3 + the conv3 forward
-#endif
-template <int EPI, int NJ = 2>
-__global__ void __launch_bounds__(512, 1) conv_ws_pre_kernel(NTArgs a) {
-  constexpr int NP = 3, CS = 64, N = 32 * NJ, K = 4 * CS, LD = K + 8, WPB = 8, G = CS / 16;
-  __shared__ __attribute__((aligned(16))) __bf16 Bs[NP][N * LD];
-  // data gradient: an out-of-grid tap reads the stage's zero position (one address select per tap
-  // instead of zeroing its 12 fragment registers; dgrad -3 us)
-  constexpr bool ZROW = EPI != EPI_CONV;
-  constexpr int SPOS = kDmaSpan + (ZROW ? 1 : 0);  // staged positions per wave (+ the zero position)
-  __shared__ __attribute__((aligned(16))) __bf16 stage[WPB][SPOS * kPreRow];
-  // the statistics' per-wave partials reuse the wave's own stage once its tiles are done
-  static_assert(N * 2 * sizeof(float) <= SPOS * kPreRow * sizeof(__bf16), "red fits a stage");
-  auto red = [&](int w) { return reinterpret_cast<float (*)[2]>(&stage[w][0]); };
-  __shared__ float bfold[N];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int idx = tid; idx < N * (K / 8); idx += WPB * 64) {
-    const int n = idx / (K / 8), k8 = (idx % (K / 8)) * 8;
-    const float4 lo = *reinterpret_cast<const float4*>(a.Bw + (int64_t)n * a.ldb + k8);
-    const float4 hi = *reinterpret_cast<const float4*>(a.Bw + (int64_t)n * a.ldb + k8 + 4);
-    bf16x8 pl[NP];
-    planes_x8<NP>(lo, hi, pl);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) *reinterpret_cast<bf16x8*>(&Bs[q][n * LD + k8]) = pl[q];
-  }
-  if (EPI == EPI_CONV && a.fold_t != nullptr) {
-    for (int q = tid; q < N * 8; q += WPB * 64) {
-      const int n = q / 8, part = q % 8;
-      double acc = 0.0;
-#pragma unroll
-      for (int c = 0; c < CS / 8; ++c) acc += a.fold_t[(int64_t)(part * (CS / 8) + c) * N + n];
-#pragma unroll
-      for (int o = 4; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-      if (part == 0) bfold[n] = (float)(acc + (double)a.bias[n]);
-    }
-  }
-  __syncthreads();
-  const int64_t W = (int64_t)gridDim.x * WPB;
-  const int64_t g = (int64_t)blockIdx.x * WPB + __builtin_amdgcn_readfirstlane(wave);
-  const int r_lo = (int)(a.M * g / W), r_hi = (int)(a.M * (g + 1) / W);
-  const int HoWo = a.Ho * a.Wo;
-  const int npos = a.Hs * a.Ws * (a.M / HoWo);
-  int tofs[4], tmin = 0, tmax = 0;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    tofs[t] = a.dh[t] * a.Ws + a.dw[t];
-    tmin = min(tmin, tofs[t]);
-    tmax = max(tmax, tofs[t]);
-  }
-  const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.src), 0, (int)std::min<int64_t>((int64_t)npos * CS * 4, 0x7ffffff0), 0x00020000);
-  const int kq = 8 * (lane >> 5);
-  float st[NJ][2];
-  float bias[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    st[j][0] = st[j][1] = 0.0f;
-    bias[j] = 0.0f;
-    if constexpr (EPI == EPI_CONV) bias[j] = a.fold_t != nullptr ? bfold[32 * j + (lane & 31)] : a.bias[32 * j + (lane & 31)];
-  }
-  __bf16* sw = stage[__builtin_amdgcn_readfirstlane(wave)];
-  if constexpr (ZROW) {
-    if (lane < kPreRow / 8) *reinterpret_cast<bf16x8*>(sw + kDmaSpan * kPreRow + lane * 8) = bf16x8{};
-  }
-  constexpr uint32_t kOOB = 0x80000000u;
-  // unit u = lane + 64 k: position u >> 1, channels cg * 16 + 8 (u & 1) .. + 7 of the group
-  auto fetch = [&](int p0, int cg, int need, float4 (&r)[2][2]) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int u = lane + 64 * k, pos = u >> 1;
-      const uint32_t off = pos < need ? (uint32_t)(((p0 + pos) * CS + cg * 16 + (u & 1) * 8) * 4) : kOOB;
-      if constexpr ((ABD_PRE_ABL & 2) != 0) {
-        typedef float fv4 __attribute__((ext_vector_type(4)));
-        fv4 z;
-        asm volatile("; abl" : "=v"(z) : "v"(off));
-        r[k][0] = r[k][1] = __builtin_bit_cast(float4, z);
-        continue;
-      }
-      r[k][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)off, 0, 0));
-      r[k][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)(off + 16u), 0, 0));
-    }
-  };
-  auto put = [&](int need, const float4 (&r)[2][2]) {
-    if constexpr ((ABD_PRE_ABL & 1) != 0) {
-      typedef float fv4 __attribute__((ext_vector_type(4)));
-      const fv4 x0 = __builtin_bit_cast(fv4, r[0][0]), x1 = __builtin_bit_cast(fv4, r[0][1]);
-      const fv4 x2 = __builtin_bit_cast(fv4, r[1][0]), x3 = __builtin_bit_cast(fv4, r[1][1]);
-      asm volatile("; abl" ::"v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(need));
-      return;
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int u = lane + 64 * k, pos = u >> 1;
-      if (pos < need) {
-        bf16x8 pl[NP];
-        if constexpr ((ABD_PRE_ABL & 16) != 0) {
-          pl[0] = __builtin_bit_cast(bf16x8, r[k][0]);
-          pl[1] = __builtin_bit_cast(bf16x8, r[k][1]);
-          pl[2] = pl[0];
-        } else {
-          planes_x8<NP>(r[k][0], r[k][1], pl);
-        }
-#pragma unroll
-        for (int q = 0; q < NP; ++q) *reinterpret_cast<bf16x8*>(sw + pos * kPreRow + q * 16 + (u & 1) * 8) = pl[q];
-      }
-    }
-  };
-  const int ntiles = (r_hi - r_lo + 31) / 32;
-  const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
-      a.out + (int64_t)r_lo * N, 0, (r_hi - r_lo) * N * 4, 0x00020000);
-  // this lane's output row m0 + (lane & 31) of the current tile as (b, h, w), stepped 32 rows per
-  // tile without dividing (the per-tile divisions of the other kernels' src_of / taps_of cost ~15 %
-  // of this kernel's VALU).  Rows past r_hi (the wave's last tile) continue the image pattern: their
-  // outputs are dropped, their taps stay inside the staged span (dma_span bounds any 32 rows), and
-  // past the last image their positions load zeros (buffer range check).
-  const int dH = 32 / a.Wo, dW = 32 - dH * a.Wo;
-  int cb, ch, cw;
-  {
-    const int m = r_lo + (lane & 31);
-    cb = m / HoWo;
-    const int rem = m - cb * HoWo;
-    ch = rem / a.Wo;
-    cw = rem - ch * a.Wo;
-  }
-  auto step32 = [&](int& b, int& h, int& w) {
-    w += dW;
-    h += dH;
-    if (w >= a.Wo) {
-      w -= a.Wo;
-      ++h;
-    }
-    while (h >= a.Ho) {
-      h -= a.Ho;
-      ++b;
-    }
-  };
-  auto src_at = [&](int b, int h, int w) { return (b * a.Hs + h) * a.Ws + w; };
-  auto taps_at = [&](int h, int w) {
-    uint32_t mk = 0;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int hs = h + a.dh[t], ws = w + a.dw[t];
-      if (hs >= 0 && hs < a.Hs && ws >= 0 && ws < a.Ws) mk |= 1u << t;
-    }
-    return mk;
-  };
-  // first staged position of the 32 rows whose lane-row source is s0, and the positions they reach
-  auto span_of = [&](int s0, int& need) {
-    int v = s0, u = s0;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-      v = min(v, __shfl_xor(v, o, 64));
-      u = max(u, __shfl_xor(u, o, 64));
-    }
-    const int base = __builtin_amdgcn_readfirstlane(v) + tmin;
-    need = __builtin_amdgcn_readfirstlane(u) + tmax + 1 - base;
-    return base;
-  };
-  // B fragments are loaded BD steps ahead (NBV buffers, a power of two: the 16 steps of a tile keep
-  // the buffer order across tiles); 2 steps ahead: forward -2, data gradient -1.5 us against 1
-  constexpr int BD = 2, NBV = 4;
-  bf16x8 bvs[NBV][NJ][NP];
-  auto load_b = [&](int cg, int t, bf16x8 (&bv)[NJ][NP]) {
-    const int kb = t * CS + cg * 16 + kq;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int q = 0; q < NP; ++q) bv[j][q] = *reinterpret_cast<const bf16x8*>(&Bs[q][(32 * j + (lane & 31)) * LD + kb]);
-  };
-  // Software pipeline over the wave's stream of groups (4 per tile): while group g's MFMAs run, its
-  // 12 A fragments are already in registers, group g + 1's planes are written to the stage (LDS
-  // executes a wave's DS instructions in order: g's reads precede the writes) and group g + 2's
-  // units are loading.
-  int need = kDmaSpan, needn = kDmaSpan;
-  int p0 = ntiles > 0 ? span_of(src_at(cb, ch, cw), need) : 0;
-  float4 raw[2][2];
-  fetch(p0, 0, ntiles > 0 ? need : 0, raw);
-  put(ntiles > 0 ? need : 0, raw);
-  fetch(p0, 1, ntiles > 0 ? need : 0, raw);
-#pragma unroll
-  for (int s = 0; s < BD; ++s) load_b(s / 4, s % 4, bvs[s]);
-#pragma unroll 1
-  for (int tile = 0; tile < ntiles; ++tile) {
-    const int m0 = r_lo + 32 * tile;
-    const int prow = src_at(cb, ch, cw) - p0;
-    const uint32_t tm = taps_at(ch, cw);
-    const bool more = tile + 1 < ntiles;
-    int nb = cb, nh = ch, nw = cw;  // the next tile's row
-    step32(nb, nh, nw);
-    const int p0n = span_of(src_at(nb, nh, nw), needn);
-    const int nn = more ? needn : 0;  // staged positions of the next tile (0: nothing to stage)
-    f32x16 acc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-#pragma unroll
-    for (int cg = 0; cg < G; ++cg) {
-      __builtin_amdgcn_sched_barrier(0);
-      bf16x8 av[4][NP];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        int pos = min(max(prow + tofs[t], 0), kDmaSpan - 1);  // an invalid tap's position is clamped
-        if constexpr (ZROW) pos = (tm >> t) & 1u ? pos : kDmaSpan;  // ... or the zero position
-        const __bf16* rp = sw + pos * kPreRow + kq;
-#pragma unroll
-        for (int q = 0; q < NP; ++q) av[t][q] = *reinterpret_cast<const bf16x8*>(rp + q * 16);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      // group g + 1 into the stage (this tile's next group, or the next tile's group 0)
-      put(cg + 1 < G ? need : nn, raw);
-      __builtin_amdgcn_sched_barrier(0);
-      // group g + 2's loads
-      if (cg + 2 < G) fetch(p0, cg + 2, need, raw);
-      else fetch(p0n, cg + 2 - G, nn, raw);
-      __builtin_amdgcn_sched_barrier(0);  // one group's loads live at a time (hoisted, they spill)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if constexpr (EPI != EPI_CONV && !ZROW) {  // data-gradient taps leave the source grid at its edges
-          if (!((tm >> t) & 1u)) {
-#pragma unroll
-            for (int q = 0; q < NP; ++q) av[t][q] = bf16x8{};
-          }
-        }
-        const int s = cg * 4 + t;
-        load_b(((s + BD) % (4 * G)) / 4, (s + BD) % 4, bvs[(s + BD) % NBV]);
-        bf16x8 (&bv)[NJ][NP] = bvs[s % NBV];
-#pragma unroll
-        for (int term = 0; term < Terms<NP>::n; ++term)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            if constexpr ((ABD_PRE_ABL & 4) != 0) {
-              asm volatile("; abl" ::"v"(av[t][Terms<NP>::A[term]]), "v"(bv[j][Terms<NP>::B[term]]));
-              continue;
-            }
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[t][Terms<NP>::A[term]], bv[j][Terms<NP>::B[term]], acc[j], 0, 0, 0);
-          }
-      }
-    }
-    p0 = p0n;
-    need = needn;
-    cb = nb;
-    ch = nh;
-    cw = nw;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      const bool ok = m < r_hi;
-      const uint32_t ob = ok ? (uint32_t)((m - r_lo) * N + (lane & 31)) * 4u : kOOB;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        float v = acc[j][r];
-        if constexpr (EPI == EPI_CONV) {
-          v = fmaxf(v + bias[j], 0.0f);
-          const float vs = ok ? v : 0.0f;
-          st[j][0] += vs;
-          st[j][1] = fmaf(vs, vs, st[j][1]);
-        }
-        if ((ABD_PRE_ABL & 8) && __builtin_bit_cast(uint32_t, v) != 0x7fc00001u) continue;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), orsrc, (int)(ob + 128u * j), 0, 0);
-      }
-    }
-  }
-  if (EPI != EPI_CONV || a.part == nullptr) return;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const float s0 = st[j][0] + __shfl_xor(st[j][0], 32, 64);
-    const float s1 = st[j][1] + __shfl_xor(st[j][1], 32, 64);
-    if (lane < 32) {
-      red(wave)[32 * j + lane][0] = s0;
-      red(wave)[32 * j + lane][1] = s1;
-    }
-  }
-  __syncthreads();
-  if (tid < N) {
-    float s0 = 0.0f, s1 = 0.0f;
-    for (int w = 0; w < WPB; ++w) {
-      s0 += red(w)[tid][0];
-      s1 += red(w)[tid][1];
-    }
-    a.part[((int64_t)0 * a.N + tid) * a.nblk + blockIdx.x] = s0;
-    a.part[((int64_t)1 * a.N + tid) * a.nblk + blockIdx.x] = s1;
-  }
-}
-
-// Weight-stationary conv GEMM in f32split with WAVE-SPECIALISED staging (round 4).  The ablations of
-// conv_ws_pre_kernel (no MFMAs: still 0.093 ms of 0.121) show its every-wave chain -- loads, split,
-// LDS writes, fragment reads, MFMAs -- bound by latency at 2 waves per SIMD, with the matrix pipe
-// ~45 % busy.  Here the two waves of a SIMD split the roles: waves 0-3 (one per SIMD) only read
+// Weight-stationary conv GEMM in f32split with the A operand staged PRE-SPLIT by WAVE-SPECIALISED
+// producers (round 4): conv2's forward and data gradient, conv3's forward.
+// Split once into three planes: splitting every (row, tap) fragment of a 16-channel group after
+// reading it from an fp32 stage (what conv_ws_dma_kernel did for f32split) is 32 rows x 4 taps of
+// splits for ~48 distinct positions, 2.7x redundant, and its LDS-DMA pieces cost 60-185 issue
+// cycles each beside MFMAs (MI355X_MICROARCH.md); with the split's VALU they crowded the issue
+// slots the MFMAs need (forward ablation: no DMA issue 0.131 -> 0.083 ms, no split -> 0.106).  So
+// a group's span is loaded with plain buffer loads (units of 8 channels x 1 position, 32 B, <= 2
+// per lane), each unit is split ONCE into the three exact bf16 planes and written to an LDS stage
+// (kPreRow = 56 bf16 = 112 B per position: 3 planes x 32 B + 16 B pad, 7 bank groups apart, so 16
+// consecutive positions hit 16 distinct groups), and the taps read the planes straight into the
+// MFMA operands (3 ds_read_b128 per tap).
+// Wave specialisation: with every wave running the whole chain -- loads, split, LDS writes,
+// fragment reads, MFMAs -- that scheme (conv_ws_pre_kernel, removed) was bound by
+// latency at 2 waves per SIMD, the matrix pipe ~45 % busy (without its MFMAs it still took 0.093
+// ms of 0.121).  Here the two waves of a SIMD split the roles: waves 0-3 (one per SIMD) only read
 // fragments and run the MFMAs and the epilogue; waves 4-7 (their SIMD partners) load the consumer's
-// span two groups ahead, split each unit once into the three exact bf16 planes and write them into
-// the consumer's double-buffered stage, so the split's VALU co-executes with the partner's MFMAs.
+// span two groups ahead, split it and write it into the consumer's double-buffered stage, so the
+// split's VALU co-executes with the partner's MFMAs.
 // One block barrier per 16-channel group publishes group q + 1 while the consumer reads group q.
 // Every wave runs the same number of groups (the longest consumer's; rows past r_hi are masked).
-// Same tiles (32 rows x 32 NJ columns per consumer tile), K order, products and epilogue as
-// conv_ws_pre_kernel, so results are identical to it.  LDS: 101,376 (weights) + 57,344 / 58,240
-// (4 consumers x 2 buffers x 64 positions x 112 B, + a zero position per buffer in the data
-// gradient) + 256 B.
-#ifndef ABD_SPEC_ABL  // measurement builds (results discarded): 1 no stage writes, 2 no loads,
-#define ABD_SPEC_ABL 0  // 4 no MFMAs, 8 no output stores, 16 no group barriers (every wave runs free),
-                        // 32 no B-fragment LDS reads (each register set loaded once)
-#endif
-#ifndef ABD_SPEC_ILV  // consumer read schedule: 3 (default) A one tap ahead and every step's reads
-#define ABD_SPEC_ILV 3  // two per MFMA gap; 2 one per gap; 1 only B interleaved; 0 all 18 reads at the
-#endif                 // group start (A/B, 3 alternations: 0 1.0007, 1 0.9916, 2 0.9894 ms per step;
-                       // 2 vs 3 on another box: forward 0.1179 vs 0.1164, data gradient 0.1223 vs 0.1207)
-#ifndef ABD_WS_SPEC  // conv_ws_spec_kernel replaces conv_ws_pre_kernel: 2 everywhere, 1 the forwards
-#define ABD_WS_SPEC 2  // only, 0 nowhere (measurement builds)
-#endif
+// Tiles of 32 rows x 32 NJ columns per consumer, K steps channel-group-major (step = 4 cg + t) as
+// in conv_ws_dma_kernel, the six products of Terms<3> per step, conv_ws_split_kernel's epilogue.
+// Consumer read schedule: A fragments one tap ahead, B two steps ahead, every step's reads two per
+// MFMA gap (against one per gap: forward 0.1179 vs 0.1164, data gradient 0.1223 vs 0.1207 ms).
+// LDS budget: 101,376 (weights) + 57,344 (stages: 4 consumers x 2 buffers x 64 positions x 112 B;
+// the data gradient's 58,240 with a zero position per buffer) + 256 = 158,976 / 159,872 B of the
+// CU's 163,840 (the statistics' per-consumer partials reuse a stage buffer after the last tile).
+constexpr int kPreRow = 56;
 // NP = 1 (bf16 mode, conv2): the A source is the producer layer's bf16 plane (NTArgs::srcs), loaded 16 B
-// per unit and stored to the stage unchanged (no split); one MFMA term per step.  Same tiles, K order
-// and products as conv_ws_dma_kernel<EPI, 1, 2, true>, whose LDS-DMA pieces stalled the issuing
-// waves' MFMAs (r6_bf16abl: without the DMA issue the bf16 forward ran 39 -> 21 us at B = 256).
-#ifndef ABD_BF16_SPEC  // measurement builds: 0 keeps bf16's conv2 on conv_ws_dma_kernel
-#define ABD_BF16_SPEC 1
-#endif
+// per unit and stored to the stage unchanged (no split); one MFMA term per step.  An LDS-DMA staging of
+// the plane stalled the issuing waves' MFMAs (r6_bf16abl: without the DMA issue the bf16 forward ran
+// 39 -> 21 us at B = 256).
 template <int EPI, int NJ = 2, int NP = 3>
 __global__ void __launch_bounds__(512, 1) conv_ws_spec_kernel(NTArgs a) {
   static_assert(NP == 3 || (NP == 1 && NJ == 2), "f32split planes, or bf16 planes for conv2");
@@ -2741,8 +2374,8 @@ __global__ void __launch_bounds__(512, 1) conv_ws_spec_kernel(NTArgs a) {
     tmax = max(tmax, tofs[t]);
   }
   constexpr uint32_t kOOB = 0x80000000u;
-  // this wave's (consumer's) output row of the current tile, stepped 32 rows per tile as in
-  // conv_ws_pre_kernel (rows past r_hi continue the pattern; past the last image they load zeros)
+  // this wave's (consumer's) output row of the current tile, stepped 32 rows per tile
+  // (rows past r_hi continue the pattern; past the last image they load zeros)
   const int dH = 32 / a.Wo, dW = 32 - dH * a.Wo;
   int cb, ch, cw;
   {
@@ -2794,29 +2427,15 @@ __global__ void __launch_bounds__(512, 1) conv_ws_spec_kernel(NTArgs a) {
           continue;
         }
         const uint32_t off = pos < need ? (uint32_t)(((p0 + pos) * CS + cg * 16 + h * 8) * 4) : kOOB;
-        if constexpr ((ABD_SPEC_ABL & 2) != 0) {
-          typedef float fv4 __attribute__((ext_vector_type(4)));
-          fv4 z;
-          asm volatile("; abl" : "=v"(z) : "v"(off));
-          r[k][0] = r[k][1] = __builtin_bit_cast(float4, z);
-          continue;
-        }
         r[k][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)off, 0, 0));
         r[k][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)(off + 16u), 0, 0));
       }
     };
     // every position of the span buffer is written (past `need` the loads returned zeros).  Unit
     // (lane, k) = channels 8 (lane >> 5) .. + 7 of position (lane & 31) + 32 k: a ds_write_b128's
-    // 8-lane bank group then writes 8 consecutive positions 112 B apart, distinct banks (the
-    // position-pair order of conv_ws_pre_kernel 2-way conflicts), and a load still touches 32 lines
+    // 8-lane bank group then writes 8 consecutive positions 112 B apart, distinct banks (a
+    // position-pair order 2-way conflicts), and a load still touches 32 lines
     auto put = [&](__bf16* sw, const float4 (&r)[2][2]) {
-      if constexpr ((ABD_SPEC_ABL & 1) != 0) {
-        typedef float fv4 __attribute__((ext_vector_type(4)));
-        const fv4 x0 = __builtin_bit_cast(fv4, r[0][0]), x1 = __builtin_bit_cast(fv4, r[0][1]);
-        const fv4 x2 = __builtin_bit_cast(fv4, r[1][0]), x3 = __builtin_bit_cast(fv4, r[1][1]);
-        asm volatile("; abl" ::"v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(sw));
-        return;
-      }
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int pos = (lane & 31) + 32 * k, h = lane >> 5;
@@ -2854,7 +2473,7 @@ __global__ void __launch_bounds__(512, 1) conv_ws_spec_kernel(NTArgs a) {
         if (cg + 1 < G || tile + 1 < nt) put(stage[c][(cg + 1) & 1], raw[(cg + 1) % 4]);
         if (cg + 1 < G) fetch(p01, cg + 1, need1, raw[(cg + 1) % 4]);
         else fetch(p02, 0, need2, raw[0]);
-        if constexpr ((ABD_SPEC_ABL & 16) == 0) __syncthreads();
+        __syncthreads();
       }
       p01 = p02;
       need1 = need2;
@@ -2885,25 +2504,15 @@ __global__ void __launch_bounds__(512, 1) conv_ws_spec_kernel(NTArgs a) {
       }
       return mk;
     };
-    constexpr int BD = 2, NBV = 4;  // B fragments two steps ahead (as conv_ws_pre_kernel)
+    constexpr int BD = 2, NBV = 4;  // B fragments two steps ahead
     bf16x8 bvs[NBV][NJ][NP];
     auto load_b = [&](int cg, int t, bf16x8 (&bv)[NJ][NP]) {
-      if constexpr ((ABD_SPEC_ABL & 32) != 0) return;  // ablation: B fragments stay in registers
       const int kb = t * CS + cg * 16 + kq;
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int q = 0; q < NP; ++q) bv[j][q] = *reinterpret_cast<const bf16x8*>(&Bs[q][(32 * j + (lane & 31)) * LD + kb]);
     };
-    if constexpr ((ABD_SPEC_ABL & 32) != 0) {  // every B register set loaded once
-#pragma unroll
-      for (int s = 0; s < NBV; ++s)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int q = 0; q < NP; ++q)
-            bvs[s][j][q] = *reinterpret_cast<const bf16x8*>(&Bs[q][(32 * j + (lane & 31)) * LD + s * CS + kq]);
-    }
 #pragma unroll
     for (int s = 0; s < BD; ++s) load_b(s / 4, s % 4, bvs[s]);
     __syncthreads();  // group 0 staged
@@ -2922,9 +2531,8 @@ __global__ void __launch_bounds__(512, 1) conv_ws_spec_kernel(NTArgs a) {
 #pragma unroll
       for (int cg = 0; cg < G; ++cg) {
         const __bf16* sw = stage[c][cg & 1];
-#if ABD_SPEC_ILV >= 2
         // A fragments one tap ahead (two register sets), B two steps ahead; each step's reads go
-        // one per MFMA gap
+        // two per MFMA gap
         bf16x8 avb[2][NP];
         auto load_a = [&](int t, bf16x8 (&av)[NP]) {
           int pos = min(max(prow + tofs[t], 0), kDmaSpan - 1);
@@ -2939,7 +2547,7 @@ __global__ void __launch_bounds__(512, 1) conv_ws_spec_kernel(NTArgs a) {
           const int s = cg * 4 + t;
           load_b(((s + BD) % (4 * G)) / 4, (s + BD) % 4, bvs[(s + BD) % NBV]);
           if (t + 1 < 4) load_a(t + 1, avb[(t + 1) & 1]);
-          constexpr int PER = ABD_SPEC_ILV >= 3 ? 2 : 1;  // reads per MFMA gap
+          constexpr int PER = 2;  // reads per MFMA gap
           constexpr int G1 = (NJ * NP + NP + PER - 1) / PER, G0 = (NJ * NP + PER - 1) / PER;
           if (t + 1 < 4) {
 #pragma unroll
@@ -2961,56 +2569,10 @@ __global__ void __launch_bounds__(512, 1) conv_ws_spec_kernel(NTArgs a) {
 #pragma unroll
           for (int term = 0; term < Terms<NP>::n; ++term)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-              if constexpr ((ABD_SPEC_ABL & 4) != 0) {
-                asm volatile("; abl" ::"v"(av[Terms<NP>::A[term]]), "v"(bv[j][Terms<NP>::B[term]]));
-                continue;
-              }
+            for (int j = 0; j < NJ; ++j)
               acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[Terms<NP>::A[term]], bv[j][Terms<NP>::B[term]], acc[j], 0, 0, 0);
-            }
         }
-#else
-        bf16x8 av[4][NP];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          int pos = min(max(prow + tofs[t], 0), kDmaSpan - 1);
-          if constexpr (ZROW) pos = (tm >> t) & 1u ? pos : kDmaSpan;
-          const __bf16* rp = sw + pos * kPreRow + kq;
-#pragma unroll
-          for (int q = 0; q < NP; ++q) av[t][q] = *reinterpret_cast<const bf16x8*>(rp + q * 16);
-        }
-        // all 12 A reads issue here (left to itself the compiler sinks each read to its first use
-        // and waits on it there: with one MFMA wave per SIMD every LDS latency was exposed)
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int s = cg * 4 + t;
-          load_b(((s + BD) % (4 * G)) / 4, (s + BD) % 4, bvs[(s + BD) % NBV]);
-#if ABD_SPEC_ILV
-          // the step's B reads one per MFMA gap instead of a burst (LDS issue stalls)
-#pragma unroll
-          for (int x = 0; x < NJ * NP; ++x) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(0x008, Terms<NP>::n * NJ - NJ * NP, 0);
-#else
-          __builtin_amdgcn_sched_barrier(0);
-#endif
-          bf16x8 (&bv)[NJ][NP] = bvs[s % NBV];
-#pragma unroll
-          for (int term = 0; term < Terms<NP>::n; ++term)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-              if constexpr ((ABD_SPEC_ABL & 4) != 0) {
-                asm volatile("; abl" ::"v"(av[t][Terms<NP>::A[term]]), "v"(bv[j][Terms<NP>::B[term]]));
-                continue;
-              }
-              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[t][Terms<NP>::A[term]], bv[j][Terms<NP>::B[term]], acc[j], 0, 0, 0);
-            }
-        }
-#endif
-        if ((ABD_SPEC_ABL & 16) == 0 && cg + 1 < G) __syncthreads();  // the last group's barrier follows the epilogue
+        if (cg + 1 < G) __syncthreads();  // the last group's barrier follows the epilogue
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -3026,11 +2588,10 @@ __global__ void __launch_bounds__(512, 1) conv_ws_spec_kernel(NTArgs a) {
             st[j][0] += vs;
             st[j][1] = fmaf(vs, vs, st[j][1]);
           }
-          if ((ABD_SPEC_ABL & 8) && __builtin_bit_cast(uint32_t, v) != 0x7fc00001u) continue;
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), orsrc, (int)(ob + 128u * j), 0, 0);
         }
       }
-      if constexpr ((ABD_SPEC_ABL & 16) == 0) __syncthreads();
+      __syncthreads();
     }
     if (EPI == EPI_CONV && a.part != nullptr) {
 #pragma unroll
@@ -3298,12 +2859,8 @@ typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 //     LDS latency is off the MFMA path and the lgkmcnt range (15) still covers the older reads.
 // NS = Qd / 16 steps and MAXS staging slots are compile-time (checked by the launcher); slots
 // past the images write a trash row (row Qd + Qs of each buffer).
-#ifndef ABD_TRP_ILV  // the next step's fragment reads PER per MFMA gap (0: one burst after term 0);
-#define ABD_TRP_ILV 2  // conv2 weight gradient 0.109 -> 0.104 ms (A/B, 3 alternations; PER 1: 0.1045)
-#endif
-#ifndef ABD_TRP_ABL  // ablation bits (measurement builds): 1 no MFMAs, 2 no staging writes, 4 no loads
-#define ABD_TRP_ABL 0
-#endif
+// The next step's fragment reads go two per MFMA gap, not in one burst after term 0: conv2 weight
+// gradient 0.109 -> 0.104 ms (A/B, 3 alternations; one per gap: 0.1045).
 // NP = 1 (ABD_PREC_BF16): one RNE-rounded bf16 plane per operand and one MFMA term (a0 b0); the
 // staging of chunk c + 1 then rides on each step's single term.
 // PS: dz and src come pre-split (WGArgs::dzs / srcs, store_planes4): a slot loads its 4 channels'
@@ -3381,10 +2938,6 @@ __global__ void __launch_bounds__(kT, 1) conv_wgrad_trp_kernel(WGArgs a) {
         const_cast<float*>(a.src) + (int64_t)b * a.Hs * Ws * CIN, 0, a.Hs * Ws * CIN * 4, 0x00020000);
 #pragma unroll
     for (int k = 0; k < MAXS; ++k) {
-      if constexpr (ABD_TRP_ABL & 4) {
-        st[k] = make_float4((float)c, 1.f, 2.f, 3.f);
-        continue;
-      }
       const uint32_t o = off0[k] == kOOB ? kOOB : off0[k] + (isdz[k] ? hdz : hsr);
       st[k] = __builtin_bit_cast(float4, isdz[k] ? __builtin_amdgcn_raw_buffer_load_b128(rdz, (int)o, 0, 0)
                                                  : __builtin_amdgcn_raw_buffer_load_b128(rsr, (int)o, 0, 0));
@@ -3392,7 +2945,6 @@ __global__ void __launch_bounds__(kT, 1) conv_wgrad_trp_kernel(WGArgs a) {
     }
   };
   auto put_slot = [&](int k, const SlotT& vv, unsigned char* buf) {
-    if constexpr (ABD_TRP_ABL & 2) return;
     if constexpr (PS) {
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<uint2*>(buf + loff[k] + pl * 128) = vv.v[pl];
@@ -3437,7 +2989,6 @@ __global__ void __launch_bounds__(kT, 1) conv_wgrad_trp_kernel(WGArgs a) {
   };
   constexpr int NTERM = Terms<NP>::n;
   auto term = [&](const Frags& F, int tm) {
-    if constexpr (ABD_TRP_ABL & 1) return;
 #pragma unroll
     for (int i = 0; i < NT; ++i)
 #pragma unroll
@@ -3461,10 +3012,9 @@ __global__ void __launch_bounds__(kT, 1) conv_wgrad_trp_kernel(WGArgs a) {
       // 1-5 also wait for most of the new reads
       __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
       if (s + 1 < NS) load_frags(cur, s + 1, F[(s + 1) & 1]);
-#if ABD_TRP_ILV
       if constexpr (NTERM > 1) {
         // the next step's reads spread over this step's MFMA gaps instead of one burst
-        constexpr int MF = (NTERM - 1) * NT * 2, RD = (NT + 2) * NP * 2, PER = ABD_TRP_ILV;
+        constexpr int MF = (NTERM - 1) * NT * 2, RD = (NT + 2) * NP * 2, PER = 2;
         constexpr int NG = (RD + PER - 1) / PER < MF ? (RD + PER - 1) / PER : MF;
         if (s + 1 < NS) {
 #pragma unroll
@@ -3476,9 +3026,6 @@ __global__ void __launch_bounds__(kT, 1) conv_wgrad_trp_kernel(WGArgs a) {
       } else {
         __builtin_amdgcn_sched_barrier(0);
       }
-#else
-      __builtin_amdgcn_sched_barrier(0);
-#endif
       if constexpr (NTERM == 1) {
 #pragma unroll
         for (int k = 0; k < MAXS; ++k)  // slot k rides on step k % NS
@@ -4316,7 +3863,7 @@ int launch_wgrad_rows(const float* dz, const float* src, int Ho, int Wo, int Hs,
 }
 
 
-// conv_ws_split_kernel / conv_ws_dma_kernel: persistent blocks, one per CU
+// conv_ws_split_kernel / conv_ws_dma_kernel / conv_ws_spec_kernel: persistent blocks, one per CU
 int ws_grid() {
   static int n = 0;
   if (n == 0) {
@@ -4331,7 +3878,7 @@ int ws_grid() {
 // only one).  Small problems (FlowMur's 32 x 13 input: conv2 has 23 k rows at B = 256) get no more
 // blocks than give every wave one 32-row tile: each block stages the whole weight operand into its
 // LDS, so the full grid would stage it 256 times for ~11 rows per wave.
-// rows_per_block: 32 per computing wave -- 8 for the split / DMA / pre-split kernels, 4 for the
+// rows_per_block: 32 per computing wave -- 8 for the split and DMA kernels, 4 for the
 // wave-specialised kernel (4 consumers + 4 producers; round 5: FlowMur's conv3 forward, M = 3,840,
 // ran 15 blocks of two serial tiles per consumer instead of 30 of one)
 int ws_blocks(int64_t M, int rows_per_block = 8 * 32) {
@@ -4343,8 +3890,9 @@ bool ws_fits(const NTArgs& a) {
   return a.taps == 4 && a.ksplit <= 1 && a.ldb == 4 * a.Cs && a.ldc == a.N &&
          (int64_t)a.Hs * a.Ws * a.Cs * 4 * (a.M / (a.Ho * a.Wo)) < 0x7ffffff0LL;
 }
-// ABD_WS_DMA: 0 direct-load kernel everywhere, 1 (default) LDS-DMA kernel for the forward GEMMs,
-// 2 LDS-DMA for the data gradients too (read at each launch: tests/test_gpu_conv_tiles.py runs all three)
+// ABD_WS_DMA: 0 direct-load kernel (conv_ws_split_kernel) everywhere, 1 (default) the staged kernels
+// where ws_kind says so, 2 the staged kernels for every data gradient too (read at each launch:
+// tests/test_gpu_conv_tiles.py runs all three)
 int ws_dma_mode() { return env_int("ABD_WS_DMA", 1); }
 // Largest staged span (positions) of any 32 consecutive output rows of conv_ws_dma_kernel: the
 // rows' source indices repeat with the image (period Ho*Wo), so every window over two images plus
@@ -4380,25 +3928,24 @@ int dma_span(const NTArgs& a) {
 }
 // Which weight-stationary kernel launch_conv_ws_split takes for these arguments (its grid -- and
 // EPI_CONV's partial count a.nblk -- depends on it: ws_nblk)
-enum WsKind { WS_SPEC, WS_PRE, WS_DMA, WS_SPLIT };
+// The staged kernels: conv_ws_spec_kernel for f32split (NP = 3) and for bf16's plane operands (PA),
+// conv_ws_dma_kernel for bf16 without them; conv_ws_split_kernel wherever ABD_WS_DMA, the taps or
+// the span rule staging out.
+enum WsKind { WS_SPEC, WS_DMA, WS_SPLIT };
 template <int EPI, int NP, bool PA>
 WsKind ws_kind(const NTArgs& a) {
+  static_assert(!PA || NP == 1, "plane operands: bf16's single plane");
   const int dma_mode = ws_dma_mode();
-  const bool dma = dma_mode == 2 || (dma_mode == 1 && (EPI == EPI_CONV || (PA && NP == 1) ||
-                                                      (ABD_WS_PRE >= 2 && NP == 3 && !PA && a.N == 64)));
+  // mode 1 stages every forward, every plane-operand GEMM and f32split's conv2 data gradient
+  const bool dma = dma_mode == 2 || (dma_mode == 1 && (EPI == EPI_CONV || PA || (NP == 3 && a.N == 64)));
   // the forward's taps never leave the source grid; the data gradient's are masked in the kernel
   const bool fwd_taps = a.dh[0] == 0 && a.dw[0] == 0 && a.dh[1] == 0 && a.dw[1] == 1 && a.dh[2] == 1 && a.dw[2] == 0 &&
                         a.dh[3] == 1 && a.dw[3] == 1 && a.Hs == a.Ho + 1 && a.Ws == a.Wo + 1;
   const bool dg_taps = a.dh[0] == 0 && a.dw[0] == 0 && a.dh[1] == 0 && a.dw[1] == -1 && a.dh[2] == -1 && a.dw[2] == 0 &&
                        a.dh[3] == -1 && a.dw[3] == -1;
-  if ((!PA || NP == 1) && dma && (a.N == 64 || (a.N == 32 && !PA)) && a.Cs == 64 &&
-      (EPI == EPI_CONV ? fwd_taps : (EPI == EPI_STORE && dg_taps)) && dma_span(a) <= kDmaSpan) {
-    constexpr bool spec = ABD_WS_SPEC >= 2 || (ABD_WS_SPEC == 1 && EPI == EPI_CONV);
-    if (PA && NP == 1) return ABD_BF16_SPEC ? WS_SPEC : WS_DMA;
-    if (NP == 3 && a.N == 64 && ABD_WS_PRE) return spec ? WS_SPEC : WS_PRE;
-    if (NP == 3 && a.N == 32 && ABD_WS_PRE >= 3) return spec ? WS_SPEC : WS_PRE;
-    return WS_DMA;
-  }
+  if (dma && (a.N == 64 || (a.N == 32 && !PA)) && a.Cs == 64 &&
+      (EPI == EPI_CONV ? fwd_taps : (EPI == EPI_STORE && dg_taps)) && dma_span(a) <= kDmaSpan)
+    return PA || NP == 3 ? WS_SPEC : WS_DMA;
   return WS_SPLIT;
 }
 template <int EPI, int NP, bool PA>
@@ -4416,20 +3963,18 @@ int launch_conv_ws_split(const NTArgs& a, hipStream_t s, int phase) {
   // K-step order (see the kernel): channel-group-major for the forward (conv2 0.147 -> 0.141 ms),
   // tap-major for the data gradient (0.133 vs 0.136 ms channel-major)
   const bool ko = EPI == EPI_CONV;
-  // LDS-DMA A operand (conv_ws_dma_kernel): the forward 0.140 -> 0.130-0.134 ms; the f32split data
-  // gradient measured no faster through it (r4_v4: 0.1309 direct vs 0.1316 staged), so it stays on
-  // the direct kernel by default (ws_dma_mode); bf16's plane-operand data gradient is staged
-  // (0.0702 -> 0.0683 ms).  conv3 (N = 32) runs the same kernels with one 32-column tile per wave.
+  // Staged A operand: the forward 0.140 -> 0.130-0.134 ms through the LDS-DMA staging; the f32split
+  // data gradient measured no faster through that (r4_v4: 0.1309 direct vs 0.1316 staged), so data
+  // gradients stay on the direct kernel by default (ws_dma_mode) except where conv_ws_spec_kernel
+  // serves them: f32split's conv2 and bf16's plane-operand one (0.0702 -> 0.0683 ms).
+  // conv3 (N = 32) runs the same kernels with one 32-column tile per wave.
   if (kind != WS_SPLIT) {
-    if constexpr (PA && NP == 1) {
-      if (kind == WS_SPEC) conv_ws_spec_kernel<EPI, 2, 1><<<dim3(nb), dim3(512), 0, s>>>(a);
-      else conv_ws_dma_kernel<EPI, 1, 2, true><<<dim3(nb), dim3(512), 0, s>>>(a);
-    } else if (kind == WS_SPEC && a.N == 64) conv_ws_spec_kernel<EPI><<<dim3(nb), dim3(512), 0, s>>>(a);
-    else if (kind == WS_SPEC) conv_ws_spec_kernel<EPI, 1><<<dim3(nb), dim3(512), 0, s>>>(a);
-    else if (kind == WS_PRE && a.N == 64) conv_ws_pre_kernel<EPI><<<dim3(nb), dim3(512), 0, s>>>(a);
-    else if (kind == WS_PRE) conv_ws_pre_kernel<EPI, 1><<<dim3(nb), dim3(512), 0, s>>>(a);
-    else if (a.N == 64) conv_ws_dma_kernel<EPI, NP><<<dim3(nb), dim3(512), 0, s>>>(a);
-    else conv_ws_dma_kernel<EPI, NP, 1><<<dim3(nb), dim3(512), 0, s>>>(a);
+    if constexpr (PA) conv_ws_spec_kernel<EPI, 2, 1><<<dim3(nb), dim3(512), 0, s>>>(a);
+    else if constexpr (NP == 3) {
+      if (a.N == 64) conv_ws_spec_kernel<EPI><<<dim3(nb), dim3(512), 0, s>>>(a);
+      else conv_ws_spec_kernel<EPI, 1><<<dim3(nb), dim3(512), 0, s>>>(a);
+    } else if (a.N == 64) conv_ws_dma_kernel<EPI><<<dim3(nb), dim3(512), 0, s>>>(a);
+    else conv_ws_dma_kernel<EPI, 1><<<dim3(nb), dim3(512), 0, s>>>(a);
   } else if (PA) {
     if (ko) conv_ws_split_kernel<EPI, 2, 64, 1, 8, 8, NP, true, true><<<dim3(nb), dim3(512), 0, s>>>(a);
     else conv_ws_split_kernel<EPI, 2, 64, 1, 8, 8, NP, true><<<dim3(nb), dim3(512), 0, s>>>(a);

@@ -14,6 +14,7 @@ KERNELS = {
              "conv_ws_pre_kernel<1, 2>", "conv_ws_pre_kernel<0, 2>", "conv_ws_pre_kernel<1, 1>",
              "conv_ws_dma_kernel<1, 3, 2", "conv_ws_split_kernel<0, 2, 64", "conv_wgrad_trp_kernel<6, 64",
              "conv_ws_dma_kernel<1, 3, 1", "conv_ws_split_kernel<0, 2, 32", "conv_wgrad_trp_kernel<4, 32",
+             "conv_ws_dma_kernel<1, 2>", "conv_ws_dma_kernel<1, 1>",   # <EPI, NJ>: bf16 without plane operands
              "conv1_wgrad_kernel", "conv1_stats_fold_kernel", "bn_bwd_apply_kernel", "bn_pool_fwd_kernel",
              "head_fwd_kernel", "head_row_kernel", "head_dgrad_kernel", "head_bwd_kernel"],
     "stft": ["stft_mel_fast_kernel", "db_dct_mfma_kernel"],

@@ -34,20 +34,26 @@ PHASE_KERNELS = {
     "conv1_stats": [("conv1_stats_fold_kernel", 0), ("conv1_stats_kernel", 0)],
     "conv2_fwd": [("conv_ws_spec_kernel<1, 2, 3>", 0), ("conv_ws_spec_kernel<1, 2, 1>", 0), ("conv_ws_spec_kernel<1, 2>", 0), ("conv_ws_pre_kernel<1, 2>", 0), ("conv_ws_dma_kernel<1, 3, 2, false>", 0),
                   ("conv_ws_dma_kernel<1, 1, 2, true>", 0), ("conv_ws_dma_kernel<1, 3, 2>", 0), ("conv_ws_dma_kernel<1, 1, 2>", 0),
-                  ("conv_ws_dma_kernel<1, 3>", 0), ("conv_ws_dma_kernel<1, 1>", 0),
+                  ("conv_ws_dma_kernel<1, 2>", 0),  # <EPI, NJ> since the kernel serves bf16 without planes only
+                  ("conv_ws_dma_kernel<1, 3>", 0),
                   ("conv_ws_dma_kernel<3>", 0), ("conv_ws_dma_kernel<1>", 0),
                   ("conv_ws_split_kernel<1, 2, 64, 1, 8, 8, 3, false, true>", 0),
                   ("conv_ws_split_kernel<1, 2, 64, 1, 8, 8, 1, true, true>", 0),
                   ("conv_ws_split_kernel<1, 2, 64, 1, 8, 8, 3, false>", 0),
                   ("conv_ws_split_kernel<1, 2, 64, 1, 8, 8, 1, true>", 0),
-                  ("conv_ws_split_kernel<1, 2, 64, 1, 8, 8, 1, false>", 0)],
+                  ("conv_ws_split_kernel<1, 2, 64, 1, 8, 8, 1, false>", 0),
+                  # the round-3 spelling <EPI, NP>; last, because <1, 1> now names conv3's <EPI, NJ>
+                  ("conv_ws_dma_kernel<1, 1>", 0)],
     "bn2_pool": [("bn_pool_fwd_kernel", 0)],
     "conv3_fwd": [("conv_ws_spec_kernel<1, 1, 3>", 0), ("conv_ws_spec_kernel<1, 1>", 0), ("conv_ws_pre_kernel<1, 1>", 0), ("conv_ws_dma_kernel<1, 3, 1, false>", 0),
                   ("conv_ws_dma_kernel<1, 1, 1, false>", 0), ("conv_ws_dma_kernel<1, 3, 1>", 0), ("conv_ws_dma_kernel<1, 1, 1>", 0),
                   ("conv_ws_split_kernel<1, 1, 64, 1, 4, 8, 3, false, true>", 0),
                   ("conv_ws_split_kernel<1, 1, 64, 1, 4, 8, 1, false, true>", 0),
                   ("conv_ws_split_kernel<1, 1, 64, 1, 4, 8, 3, false>", 0),
-                  ("conv_ws_split_kernel<1, 1, 64, 1, 4, 8, 1, false>", 0)],
+                  ("conv_ws_split_kernel<1, 1, 64, 1, 4, 8, 1, false>", 0),
+                  # <EPI, NJ>; after the split spellings, because a round-3 bf16 profile ran conv3 on those and
+                  # spells conv2's forward <1, 1> (<EPI, NP>); conv3 never runs both in one step
+                  ("conv_ws_dma_kernel<1, 1>", 0)],
     "bn3_pool_dropout": [("bn_pool_fwd_kernel", 1)],
     "head_fwd": [("head_fwd_kernel<4>", 0), ("head_fwd_kernel<8>", 0), ("head_fwd_kernel", 0)],
     "head_mid": [("head_row_kernel", 0), ("head_mid_kernel", 0)],

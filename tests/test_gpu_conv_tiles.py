@@ -1,5 +1,6 @@
 """GPU: the weight-stationary conv2 / conv3 forward GEMMs at bench sizes, where every wave walks
-several 32-row tiles (the tile-boundary hand-off of conv_ws_dma_kernel's LDS-DMA staging).
+several 32-row tiles (the tile-boundary hand-off of the staged kernels: conv_ws_dma_kernel's LDS-DMA
+staging, now bf16's GEMMs without plane operands, and conv_ws_spec_kernel's producer waves).
 
 ADVICE r3 (high): the first wait of a later tile left ``vmcnt(32)`` loads/stores in flight, which
 is the previous epilogue's store count only for NJ = 2 (conv2).  conv3 runs NJ = 1 (16 stores),
@@ -7,7 +8,7 @@ so the wait never waited and a wave could read the previous tile's staged data. 
 of a train step are recomputed from the device's OWN input buffers (p2; m and BN1's folded
 coefficients) in float64 and compared element-wise -- a stale staged group is a whole-row error --
 and three identical launches must agree bit for bit (a race is a nondeterminism).  The data
-gradients dp2 / dp1 (the same kernels with EPI_STORE, LDS-DMA under ABD_WS_DMA=2) likewise.
+gradients dp2 / dp1 (the same kernels with EPI_STORE, staged under ABD_WS_DMA=2) likewise.
 """
 import numpy as np
 import pytest
@@ -48,7 +49,8 @@ def conv_t(dz_nhwc, w, dev):
 @pytest.mark.parametrize("shape", [(100, 40, 35, 512), (101, 40, 10, 256), (32, 13, 10, 333)])
 def test_conv_forward_tiles_match_own_inputs(shape, prec, ws_dma, monkeypatch):
     """ws_dma: ABD_WS_DMA (read at each launch) -- 0 the direct-load weight-stationary kernels
-    everywhere, 1 (default) the LDS-DMA kernel for the forward GEMMs, 2 for the data gradients too."""
+    everywhere, 1 (default) the staged kernels (conv_ws_spec_kernel, conv_ws_dma_kernel) for the forward
+    GEMMs, conv2's f32split data gradient and the plane-operand GEMMs, 2 for every data gradient too."""
     monkeypatch.setenv("ABD_WS_DMA", ws_dma)
     assert torch.cuda.is_available()
     abd_amd.load_library()
