@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <vector>
 
@@ -60,11 +61,31 @@ struct FxDev {
 __device__ __forceinline__ float sat_lut(const float* __restrict__ lut, float x) {
   // juce::dsp::LookupTableTransform::processSample: clamp, scale, truncate, lerp
   const float xc = fminf(fmaxf(x, -5.0f), 5.0f);
-  const float idx = 12.7f * xc + 63.5f;
+  const float idx = __fmaf_rn(12.7f, xc, 63.5f);
   const unsigned i = (unsigned)idx;
   const float f = idx - (float)i;
   const float x0 = lut[i], x1 = lut[i + 1];
-  return x0 + f * (x1 - x0);
+  return __fmaf_rn(f, x1 - x0, x0);
+}
+
+// One sample of juce::dsp::LadderFilter::processSample on the state s0 .. s4, shared by both board kernels.
+// Every operation is written out (no contraction left to the compiler), so the two kernels round alike: at
+// resonance 1 the feedback amplifies a differently placed fma to 4e-6 of the output.
+__device__ __forceinline__ float ladder_step(const FxDev& d, const float* __restrict__ lut, float x, float& s0,
+                                             float& s1, float& s2, float& s3, float& s4) {
+  const float dx = __fmul_rn(d.lgain, sat_lut(lut, __fmul_rn(d.ldrive, x)));
+  const float fb = __fmaf_rn(d.lgain2, sat_lut(lut, __fmul_rn(d.ldrive2, s4)), -__fmul_rn(dx, d.lcomp));
+  const float a = __fmaf_rn(__fmul_rn(d.lres, -4.0f), fb, dx);
+  const float b = __fmaf_rn(d.lb0, a, __fmaf_rn(d.la1, s1, __fmul_rn(d.lb1, s0)));
+  const float c = __fmaf_rn(d.lb0, b, __fmaf_rn(d.la1, s2, __fmul_rn(d.lb1, s1)));
+  const float e3 = __fmaf_rn(d.lb0, c, __fmaf_rn(d.la1, s3, __fmul_rn(d.lb1, s2)));
+  const float e4 = __fmaf_rn(d.lb0, e3, __fmaf_rn(d.la1, s4, __fmul_rn(d.lb1, s3)));
+  s0 = a;
+  s1 = b;
+  s2 = c;
+  s3 = e3;
+  s4 = e4;
+  return __fmaf_rn(e4, d.lA[4], __fmaf_rn(e3, d.lA[3], __fmaf_rn(c, d.lA[2], __fmaf_rn(b, d.lA[1], __fmul_rn(a, d.lA[0])))));
 }
 
 struct Chain {
@@ -101,18 +122,7 @@ __device__ __forceinline__ float run_chain(const FxDev& d, Chain& c, float x, in
         x = tanhf(x * d.gain[e]);
         break;
       case ABD_FX_LADDER: {
-        const float dx = d.lgain * sat_lut(d.lut, d.ldrive * x);
-        const float a = dx + d.lres * -4.0f * (d.lgain2 * sat_lut(d.lut, d.ldrive2 * c.ls[4]) - dx * d.lcomp);
-        const float b = d.lb1 * c.ls[0] + d.la1 * c.ls[1] + d.lb0 * a;
-        const float cc = d.lb1 * c.ls[1] + d.la1 * c.ls[2] + d.lb0 * b;
-        const float dd = d.lb1 * c.ls[2] + d.la1 * c.ls[3] + d.lb0 * cc;
-        const float ee = d.lb1 * c.ls[3] + d.la1 * c.ls[4] + d.lb0 * dd;
-        c.ls[0] = a;
-        c.ls[1] = b;
-        c.ls[2] = cc;
-        c.ls[3] = dd;
-        c.ls[4] = ee;
-        x = a * d.lA[0] + b * d.lA[1] + cc * d.lA[2] + dd * d.lA[3] + ee * d.lA[4];
+        x = ladder_step(d, d.lut, x, c.ls[0], c.ls[1], c.ls[2], c.ls[3], c.ls[4]);
         break;
       }
       case ABD_FX_CHORUS: {  // juce::dsp::Chorus, feedback 0: linear-interpolated delay of the input
@@ -192,7 +202,10 @@ __global__ void __launch_bounds__(kThreads) board_kernel(FxDev d, const float* _
   c.rbuf = ws ? ws + u : nullptr;
   if (ws)  // reset=True: zeroed reverb buffers for every clip
     for (int64_t i = 0; i < d.rstride; ++i) c.rbuf[i * ws_pitch] = 0.0f;
-  const bool vec = ((in_stride | out_stride) & 3) == 0;
+  // float4 rows: both strides multiples of 4 floats and this thread's two row pointers on 16 bytes (a view
+  // such as x[:, 1:] of a padded table has conforming strides and a base 4 bytes off)
+  const bool vec = ((in_stride | out_stride) & 3) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
   int64_t t = 0;
   if (vec) {
     for (; t + 4 <= length; t += 4) {
@@ -239,18 +252,7 @@ __global__ void __launch_bounds__(kThreads) board_fast_kernel(FxDev d, int gi, i
       if (GAIN) v = v * g;
       if (DIST) v = tanhf(v * gd);
       if (LADDER) {
-        const float dx = d.lgain * sat_lut(lut, d.ldrive * v);
-        const float a = dx + d.lres * -4.0f * (d.lgain2 * sat_lut(lut, d.ldrive2 * ls4) - dx * d.lcomp);
-        const float b = d.lb1 * ls0 + d.la1 * ls1 + d.lb0 * a;
-        const float c = d.lb1 * ls1 + d.la1 * ls2 + d.lb0 * b;
-        const float e3 = d.lb1 * ls2 + d.la1 * ls3 + d.lb0 * c;
-        const float e4 = d.lb1 * ls3 + d.la1 * ls4 + d.lb0 * e3;
-        ls0 = a;
-        ls1 = b;
-        ls2 = c;
-        ls3 = e3;
-        ls4 = e4;
-        v = a * d.lA[0] + b * d.lA[1] + c * d.lA[2] + e3 * d.lA[3] + e4 * d.lA[4];
+        v = ladder_step(d, lut, v, ls0, ls1, ls2, ls3, ls4);
       }
     }
     if (PHASER) {  // stage B: phaser of sample t - 1 (independent of stage A above)
@@ -513,6 +515,21 @@ PitchWs pitch_ws(const PitchDev& p, int64_t batch, int64_t length, bool need_out
 // ---- host-side JUCE restatements (float, like the plugins) --------------------------------
 float decibels_to_gain(float db) { return db > -100.0f ? std::pow(10.0f, db * 0.05f) : 0.0f; }
 
+bool all_finite(const float* v, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+// parameters p[0 .. n) an effect kind reads (include/abd.h)
+int fx_param_count(int kind) {
+  static const int n[7] = {1, 1, 4, 5, 5, 6, 1};
+  return kind >= 0 && kind <= ABD_FX_PITCHSHIFT ? n[kind] : 0;
+}
+const char* fx_name(int kind) {
+  static const char* const name[7] = {"Gain", "Distortion", "LadderFilter", "Phaser", "Chorus", "Reverb", "PitchShift"};
+  return kind >= 0 && kind <= ABD_FX_PITCHSHIFT ? name[kind] : "unknown effect";
+}
+
 }  // namespace
 
 struct abd_style_board {
@@ -569,6 +586,8 @@ int abd_style_board_create(const abd_effect* fx, int n, int sample_rate, int64_t
   for (int e = 0; e < n; ++e) {
     const abd_effect& f = fx[e];
     d.kind[e] = f.kind;
+    ABD_CHECK(all_finite(f.p, (size_t)fx_param_count(f.kind)), ABD_E_INVALID, "%s (effect %d): a parameter is not finite",
+              fx_name(f.kind), e);
     switch (f.kind) {
       case ABD_FX_GAIN:
       case ABD_FX_DISTORTION:
@@ -620,7 +639,9 @@ int abd_style_board_create(const abd_effect* fx, int n, int sample_rate, int64_t
         for (int64_t k = 0; k < steps; ++k) {
           const float last = phase;  // Phase::advance returns the pre-increment phase
           float next = last + inc;
-          while (next >= two_pi) next -= two_pi;
+          // JUCE subtracts 2 pi until it fits; fmod is that subtraction (exact) while rate_hz <= the LFO's rate,
+          // and still ends where a huge finite rate_hz makes the subtraction stop moving a float
+          if (next >= two_pi) next = std::fmod(next, two_pi);
           phase = next;
           const float lfo = std::min(1.0f, std::max(0.0f, std::sin(last - pi) * vol + norm));
           const float cut = std::pow(10.0f, lfo * (std::log10(hi) - std::log10(lo)) + std::log10(lo));
@@ -650,7 +671,9 @@ int abd_style_board_create(const abd_effect* fx, int n, int sample_rate, int64_t
         for (int64_t k = 0; k < max_length; ++k) {
           const float last = phase;
           float next = last + inc;
-          while (next >= two_pi) next -= two_pi;
+          // JUCE subtracts 2 pi until it fits; fmod is that subtraction (exact) while rate_hz <= the LFO's rate,
+          // and still ends where a huge finite rate_hz makes the subtraction stop moving a float
+          if (next >= two_pi) next = std::fmod(next, two_pi);
           phase = next;
           const float lfo = std::max(1.0f, 20.0f * (std::sin(last - pi) * vol) + cdelay);
           const float ds = (float)((double)lfo * (double)sample_rate / 1000.0);
@@ -670,7 +693,7 @@ int abd_style_board_create(const abd_effect* fx, int n, int sample_rate, int64_t
         int off = 0;
         for (int j = 0; j < 12; ++j) {
           const int tuning = j < 8 ? comb[j] : ap[j - 8];
-          d.rsize[j] = std::max(1, (sample_rate * tuning) / 44100);
+          d.rsize[j] = (int)std::max<int64_t>(1, ((int64_t)sample_rate * tuning) / 44100);  // past int from 1.33 MHz
           d.roff[j] = off;
           off += d.rsize[j];
         }
@@ -687,6 +710,23 @@ int abd_style_board_create(const abd_effect* fx, int n, int sample_rate, int64_t
       default:
         ABD_CHECK(false, ABD_E_UNSUPPORTED, "effect kind %d is not accelerated", f.kind);
     }
+  }
+  // Finite parameters can still make tables the kernels cannot run (a LadderFilter drive of 0 or below: its
+  // gain drive^-2.642 is inf or NaN).  Finite values outside JUCE's debug assertions pass, as they do there.
+  {
+    const float ladder[] = {d.la1, d.lb0, d.lb1, d.ldrive, d.ldrive2, d.lgain, d.lgain2, d.lres, d.lcomp,
+                            d.lA[0], d.lA[1], d.lA[2], d.lA[3], d.lA[4]};
+    const float phaser[] = {d.pfeedback, d.pdry, d.pwet};
+    const float chorus[] = {d.cdry, d.cwet};
+    const float reverb[] = {d.rgain, d.rdamp, d.rfb, d.rdry, d.rwet};
+    ABD_CHECK(all_finite(d.gain, kMaxFx), ABD_E_INVALID, "Gain / Distortion: the linear gain is not finite");
+    ABD_CHECK(all_finite(ladder, sizeof(ladder) / sizeof(float)) && all_finite(lut.data(), lut.size()), ABD_E_INVALID,
+              "LadderFilter: a coefficient is not finite (drive %g: the gain is drive^-2.642)", d.ldrive);
+    ABD_CHECK(all_finite(phaser, 3) && all_finite(G.data(), G.size()), ABD_E_INVALID,
+              "Phaser: the allpass coefficient table is not finite");
+    ABD_CHECK(all_finite(chorus, 2) && all_finite(CD.data(), CD.size()), ABD_E_INVALID,
+              "Chorus: the delay table is not finite");
+    ABD_CHECK(all_finite(reverb, 5), ABD_E_INVALID, "Reverb: a coefficient is not finite");
   }
   auto* b = new abd_style_board{};
   const size_t nfl = (size_t)(kLut + 1) + G.size() + CD.size();

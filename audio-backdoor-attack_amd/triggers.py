@@ -299,6 +299,9 @@ class Pedalboard:
         """waves (N, L) float32 on the device -> (B, L) effected rows (rows int32 gathers, None = all)."""
         L.require_device(waves, "waves")
         assert waves.dtype == torch.float32 and waves.dim() == 2
+        if rows is not None and not (rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous()
+                                     and rows.device == waves.device):
+            raise L.AbdError("rows: a contiguous 1-D int32 tensor on the device of waves")
         B = rows.numel() if rows is not None else waves.shape[0]
         Ln = waves.shape[1]
         out = torch.empty((B, Ln), dtype=torch.float32, device=waves.device)

@@ -227,7 +227,25 @@ int abd_resample_f32(const abd_resample_plan* plan, const float* in, int64_t in_
  *               then a resample by 1/r); no bit-level spec is public, so this is a phase vocoder of
  *               the same structure defined in oracle/effects.py (pitch_shift): parity unpinned.
  *   Effects between the board's start (after a PitchShift) and a Chorus must be memoryless (Gain,
- *   Distortion): the chorus delay line re-applies them to the history it reads. */
+ *   Distortion): the chorus delay line re-applies them to the history it reads.
+ *
+ * Accepted range (tests/style_envelope_cases.py walks it, profiles/styles/envelope.md reports it):
+ *   abd_style_board_create   0 <= n <= 8 effects (n = 0, or a lone PitchShift: the chain is a copy);
+ *     sample_rate > 0 (the reverb sizes sample_rate * tuning / 44100 are formed in 64 bits);
+ *     max_length >= 0; semitones in [-24, 24]; every parameter finite, and every derived
+ *     coefficient and table entry finite -- a LadderFilter drive <= 0 is refused (its gain is
+ *     drive^-2.642), ABD_E_INVALID naming the effect.  Finite values outside JUCE's debug
+ *     assertions run as JUCE's release build runs them: Chorus depth 5 (the reference's own),
+ *     centre_delay_ms outside [1, 100] (clamped), a Phaser centre_frequency_hz <= 0 (the LFO's
+ *     lower clamp), mix / resonance / room_size outside [0, 1], any finite rate_hz (the LFO's phase
+ *     is reduced with fmod: the same value as JUCE's repeated subtraction up to the LFO's own rate).  A second LadderFilter, Phaser or
+ *     Reverb, a Chorus feedback != 0, a stateful effect before a Chorus, a PitchShift that is
+ *     not first: ABD_E_UNSUPPORTED.
+ *   abd_style_board_apply    any batch >= 0 (a PitchShift board: <= 65535), 0 <= length <=
+ *     max_length (a plan made for a longer clip gives bit for bit what a plan of that length
+ *     gives), in_stride and out_stride >= length, any alignment of in / out (the 16-byte path is
+ *     taken only where both row pointers allow it), rows with repeats.  Samples of a row are
+ *     adjacent: there is no element stride. */
 enum { ABD_FX_GAIN = 0, ABD_FX_DISTORTION = 1, ABD_FX_LADDER = 2, ABD_FX_PHASER = 3, ABD_FX_CHORUS = 4,
        ABD_FX_REVERB = 5, ABD_FX_PITCHSHIFT = 6 };
 typedef struct abd_effect {

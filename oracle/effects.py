@@ -15,7 +15,9 @@ not installed here: parity unpinned):
     stages G = tan(pi fc / sr) / (1 + tan(.)): v = G (x - s), y = v + s, s = y + v, out = 2y - x;
     feedback of the stage output; out = mix * wet + (1 - mix) * dry.
 The LFO and the saturation table are computed in float32 like the plugin (they are coefficient
-tables); the per-sample recursions run in float64.
+tables); the per-sample recursions run in float64, or -- ``dtype=np.float32`` -- in float32 with the
+same tables: the distance between the two is what the number format alone costs, the condition the
+device bounds of tests/style_envelope_cases.py rest on.  ``board`` runs an arbitrary chain.
 """
 from __future__ import annotations
 
@@ -38,10 +40,11 @@ def sat_table():
 
 
 def sat(tab, x):
-    xc = np.clip(x, -5.0, 5.0)
-    idx = 12.7 * xc + 63.5
+    dt = tab.dtype.type
+    xc = np.clip(x, dt(-5.0), dt(5.0))
+    idx = dt(12.7) * xc + dt(63.5)
     i = np.floor(idx).astype(np.int64)
-    f = idx - i
+    f = idx - i.astype(tab.dtype)
     return tab[i] + f * (tab[i + 1] - tab[i])
 
 
@@ -50,8 +53,9 @@ LADDER_A = np.array([[0, 0, 1, 0, 0], [1, -2, 1, 0, 0], [0, 0, -1, 1, 0], [0, 0,
 LADDER_COMP = [0.5, 0.0, 0.5, 0.5, 0.0, 0.5]
 
 
-def ladder(x, sr, mode=0, cutoff_hz=200.0, resonance=0.0, drive=1.0):
-    """(B, L) float64 -> (B, L)."""
+def ladder(x, sr, mode=0, cutoff_hz=200.0, resonance=0.0, drive=1.0, dtype=np.float64):
+    """(B, L) -> (B, L) in ``dtype`` (the coefficients rounded to it, every per-sample operation in it)."""
+    x = np.asarray(x, dtype=dtype)
     a1 = math.exp(cutoff_hz * (-2.0 * math.pi / sr))
     g = 1.0 - a1
     b0, b1 = g * 0.76923076923, g * 0.23076923076
@@ -59,13 +63,15 @@ def ladder(x, sr, mode=0, cutoff_hz=200.0, resonance=0.0, drive=1.0):
     gain = drive ** -2.642 * 0.6103 + 0.3903
     drive2 = drive * 0.04 + 0.96
     gain2 = drive2 ** -2.642 * 0.6103 + 0.3903
-    A, comp = LADDER_A[mode], LADDER_COMP[mode]
-    tab = sat_table()
-    s = np.zeros((5, x.shape[0]))
+    comp = LADDER_COMP[mode]
+    a1, b0, b1, res, gain, drive, drive2, gain2, comp = (dtype(v) for v in (a1, b0, b1, res, gain, drive, drive2, gain2, comp))
+    A = LADDER_A[mode].astype(dtype)
+    tab = sat_table().astype(dtype)
+    s = np.zeros((5, x.shape[0]), dtype)
     y = np.empty_like(x)
     for t in range(x.shape[1]):
         dx = gain * sat(tab, drive * x[:, t])
-        a = dx + res * -4.0 * (gain2 * sat(tab, drive2 * s[4]) - dx * comp)
+        a = dx + res * dtype(-4.0) * (gain2 * sat(tab, drive2 * s[4]) - dx * comp)
         b = b1 * s[0] + a1 * s[1] + b0 * a
         c = b1 * s[1] + a1 * s[2] + b0 * b
         d = b1 * s[2] + a1 * s[3] + b0 * c
@@ -89,8 +95,8 @@ def phaser_G(n_steps, sr, rate_hz=1.0, depth=0.5, centre_frequency_hz=1300.0):
     for k in range(n_steps):
         last = ph
         nx = F32(last + inc)
-        while nx >= two_pi:
-            nx = F32(nx - two_pi)
+        if nx >= two_pi:                    # JUCE's repeated subtraction: one exact step unless rate_hz > the LFO's rate
+            nx = F32(np.fmod(nx, two_pi))
         ph = nx
         lfo = min(F32(1.0), max(F32(0.0), F32(np.sin(F32(last - pi)) * vol + norm)))
         cut = np.power(F32(10.0), F32(lfo * (np.log10(hi) - np.log10(lo)) + np.log10(lo)))
@@ -99,10 +105,12 @@ def phaser_G(n_steps, sr, rate_hz=1.0, depth=0.5, centre_frequency_hz=1300.0):
     return G
 
 
-def phaser(x, sr, rate_hz=1.0, depth=0.5, centre_frequency_hz=1300.0, feedback=0.0, mix=0.5):
-    G = phaser_G((x.shape[1] + 3) // 4, sr, rate_hz, depth, centre_frequency_hz)
-    s = np.zeros((6, x.shape[0]))
-    last = np.zeros(x.shape[0])
+def phaser(x, sr, rate_hz=1.0, depth=0.5, centre_frequency_hz=1300.0, feedback=0.0, mix=0.5, dtype=np.float64):
+    x = np.asarray(x, dtype=dtype)
+    G = phaser_G((x.shape[1] + 3) // 4, sr, rate_hz, depth, centre_frequency_hz).astype(dtype)
+    feedback, wet, dry, two = dtype(feedback), dtype(mix), dtype(1.0) - dtype(mix), dtype(2.0)
+    s = np.zeros((6, x.shape[0]), dtype)
+    last = np.zeros(x.shape[0], dtype)
     y = np.empty_like(x)
     for t in range(x.shape[1]):
         g = G[t >> 2]
@@ -111,9 +119,9 @@ def phaser(x, sr, rate_hz=1.0, depth=0.5, centre_frequency_hz=1300.0, feedback=0
             v = g * (o - s[n])
             yy = v + s[n]
             s[n] = yy + v
-            o = 2.0 * yy - o
+            o = two * yy - o
         last = o * feedback
-        y[:, t] = o * mix + x[:, t] * (1.0 - mix)
+        y[:, t] = o * wet + x[:, t] * dry
     return y
 
 
@@ -142,28 +150,36 @@ def chorus_delays(n, sr, rate_hz=1.0, depth=0.25, centre_delay_ms=7.0):
     for k in range(n):
         last = ph
         nx = F32(last + inc)
-        while nx >= two_pi:
-            nx = F32(nx - two_pi)
+        if nx >= two_pi:                    # JUCE's repeated subtraction: one exact step unless rate_hz > the LFO's rate
+            nx = F32(np.fmod(nx, two_pi))
         ph = nx
         lfo = max(F32(1.0), F32(F32(20.0) * F32(np.sin(F32(last - pi)) * vol) + centre))
         out[k] = min(float(max_delay), max(0.0, float(F32(float(lfo) * sr / 1000.0))))
     return out
 
 
-def chorus(x, sr, rate_hz=1.0, depth=0.25, centre_delay_ms=7.0, feedback=0.0, mix=0.5):
+def chorus_history(sr):
+    """Samples of zero history in front of a clip: the delay line's maximum (chorus_delays' max_delay,
+    110 ms) plus the interpolation's second tap and one to spare, so no index reaches below 0."""
+    return math.ceil((20.0 * 1.0 * 0.5 + 100.0) * sr / 1000.0) + 2
+
+
+def chorus(x, sr, rate_hz=1.0, depth=0.25, centre_delay_ms=7.0, feedback=0.0, mix=0.5, dtype=np.float64):
     """feedback 0: wet[t] = lerp(x[t - d], x[t - d - 1], frac(d)), out = mix wet + (1 - mix) x."""
     assert feedback == 0.0
-    x = np.asarray(x, dtype=np.float64)
+    x = np.asarray(x, dtype=dtype)
     n = x.shape[1]
     d = chorus_delays(n, sr, rate_hz, depth, centre_delay_ms)
     di = np.floor(d).astype(np.int64)
-    fr = d - di
+    fr = (d - di).astype(dtype)             # the float32 table's fraction: exact in either precision
     t = np.arange(n)
-    xp = np.concatenate([np.zeros((x.shape[0], 2000)), x], axis=1)   # history before t = 0 is zero
-    v1 = xp[:, 2000 + t - di]
-    v2 = xp[:, 2000 + t - di - 1]
+    pad = chorus_history(sr)
+    xp = np.concatenate([np.zeros((x.shape[0], pad), dtype), x], axis=1)   # history before t = 0 is zero
+    assert (pad + t - di - 1).min() >= 0
+    v1 = xp[:, pad + t - di]
+    v2 = xp[:, pad + t - di - 1]
     wet = v1 + fr * (v2 - v1)
-    return wet * mix + x * (1.0 - mix)
+    return wet * dtype(mix) + x * (dtype(1.0) - dtype(mix))
 
 
 def _undenorm(v):
@@ -171,8 +187,9 @@ def _undenorm(v):
     return ((v.astype(F32) + F32(0.1)).astype(F32) - F32(0.1)).astype(F32)
 
 
-def reverb(x, sr, room_size=0.5, damping=0.5, wet_level=0.33, dry_level=0.4, width=1.0):
-    """juce::Reverb::processMono, in float32 like the plugin (the undenormalise quantisation matters)."""
+def reverb(x, sr, room_size=0.5, damping=0.5, wet_level=0.33, dry_level=0.4, width=1.0, freeze_mode=0.0):
+    """juce::Reverb::processMono, in float32 like the plugin (the undenormalise quantisation matters).
+    freeze_mode >= 0.5 (juce::Reverb::updateDamping): input gain 0, damping 0, feedback 1."""
     x = np.asarray(x, dtype=F32)
     combs = [1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617]
     aps = [556, 441, 341, 225]
@@ -185,6 +202,8 @@ def reverb(x, sr, room_size=0.5, damping=0.5, wet_level=0.33, dry_level=0.4, wid
     ci = [0] * 8
     ai = [0] * 4
     gain, damp, fb = F32(0.015), F32(damping) * F32(0.4), F32(room_size) * F32(0.28) + F32(0.7)
+    if freeze_mode >= 0.5:
+        gain, damp, fb = F32(0.0), F32(0.0), F32(1.0)
     dry = F32(dry_level) * F32(2.0)
     wet1 = F32(0.5) * (F32(wet_level) * F32(3.0)) * (F32(1.0) + F32(width))
     y = np.empty((B, n), F32)
@@ -254,8 +273,9 @@ def _princarg(x):
     return x - 2 * np.pi * np.rint(x / (2 * np.pi))
 
 
-def pitch_shift(x, sr, semitones=10.0, replay=None, tie_tol=2e-3):
-    """(B, L) -> (B, L) float64.
+def pitch_shift(x, sr, semitones=10.0, replay=None, tie_tol=2e-3, stats=None):
+    """(B, L) -> (B, L) float64.  ``stats`` (a dict): filled with the oracle's own count of near-ties
+    (``near_ties``: wrap decisions of live bins with dphi within ``tie_tol`` radians of +-pi) and the number of bins (``bins`` = B T K).
 
     Decision replay (tests): the wrap of dphi -- princarg's choice of the nearest multiple of 2 pi
     -- is a discrete decision that r's non-integer multiplier turns into a 2 pi (r - 1) jump of
@@ -280,14 +300,15 @@ def pitch_shift(x, sr, semitones=10.0, replay=None, tie_tol=2e-3):
     k = np.arange(K)
     ps = np.empty_like(pha)
     ps[:, 0] = pha[:, 0]
-    nrep = 0
+    nrep = nties = 0
     for t in range(1, T):
         h = int(ia[t] - ia[t - 1])
         raw = pha[:, t] - pha[:, t - 1] - 2 * np.pi * ((k * h) % N) / N
         dphi = _princarg(raw)
+        nties += int(((np.pi - np.abs(dphi) < tie_tol) & (mag[:, t] > 0)).sum())
         base = ps[:, t - 1] + 2 * np.pi * ((k * Hs) % N) / N
         ps[:, t] = _princarg(base + (Hs / h) * dphi)
-        if replay is not None:
+        if replay is not None and Hs % h != 0:     # Hs / h whole: every wrap gives the same phi_s, no decision
             dev = np.angle(replay[:, t])
             live = np.abs(replay[:, t]) > 0
             best = np.abs(np.angle(np.exp(1j * (ps[:, t] - dev))))
@@ -302,6 +323,8 @@ def pitch_shift(x, sr, semitones=10.0, replay=None, tie_tol=2e-3):
                     ps[:, t][take] = cand[take]
                     best = np.where(take, dist, best)
                     nrep += int(take.sum())
+    if stats is not None:
+        stats.update(near_ties=nties, bins=int(mag.size))
     Y = mag * np.exp(1j * ps)
     y = np.fft.irfft(Y, n=N, axis=2) * w                                # (B, T, N)
     ys = np.zeros((B, Ls + 2 * N))
@@ -336,3 +359,38 @@ def style3(x, sr=16000, shifted=None):
     ``shifted``: the PitchShift output to continue from (decision-replayed runs)."""
     y = np.tanh((pitch_shift(x, sr, 10.0) if shifted is None else shifted) * db_to_gain(20.0))
     return chorus(y, sr, 1.0, 5.0, 8.0, 0.0, 0.5)
+
+
+# ------------------------------------------------------------------ an arbitrary chain
+def board(x, sr, plugins, dtype=np.float64, replay=None, stats=None):
+    """Run a chain: ``plugins`` = [(name, {parameter: value}), ...] with the names and parameters of
+    abd_amd.triggers' effect classes (Gain, Distortion, LadderFilter, Phaser, Chorus, Reverb,
+    PitchShift).  Each effect reads the one before it -- the Chorus delays its own input, as in
+    style3.  ``dtype``: precision of the Gain / Distortion / LadderFilter / Phaser / Chorus stages
+    (the Reverb is float32 and the PitchShift float64 in either).  ``replay`` / ``stats``: handed to
+    pitch_shift; with ``replay`` the result is (out, replayed decisions)."""
+    y = np.asarray(x, dtype=np.float64)
+    nrep = 0
+    for i, (name, kw) in enumerate(plugins):
+        if name == "PitchShift":
+            assert i == 0, "PitchShift opens a board only"
+            if replay is not None:
+                y, nrep = pitch_shift(y, sr, kw.get("semitones", 0.0), replay=replay, stats=stats)
+            else:
+                y = pitch_shift(y, sr, kw.get("semitones", 0.0), stats=stats)
+        elif name == "Gain":
+            y = np.asarray(y, dtype) * dtype(db_to_gain(kw.get("gain_db", 1.0)))
+        elif name == "Distortion":
+            y = np.tanh(np.asarray(y, dtype) * dtype(db_to_gain(kw.get("drive_db", 25.0))))
+        elif name == "LadderFilter":
+            y = ladder(y, sr, dtype=dtype, **kw)
+        elif name == "Phaser":
+            y = phaser(y, sr, dtype=dtype, **kw)
+        elif name == "Chorus":
+            y = chorus(y, sr, dtype=dtype, **kw)
+        elif name == "Reverb":
+            y = reverb(y, sr, **kw)
+        else:
+            raise ValueError(f"unknown effect {name}")
+    y = np.asarray(y, dtype=np.float64)
+    return (y, nrep) if replay is not None else y
