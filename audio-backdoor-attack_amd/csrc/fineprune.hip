@@ -11,20 +11,17 @@
 // fixed order (per-lane strided sums in double, a butterfly over the wave); there are no
 // floating-point atomics, so equal inputs give bit-equal results.
 #include <cmath>
+#include <type_traits>
 
 #include "abd_common.h"
 
 namespace {
 
-constexpr int kT = 256;
+// kT, grid_for, round256, AdamConsts / adam_elem_stored, no_update_args, checks
+#include "defense_common.inc"
+
 constexpr int kUnits = ABD_FCPRUNE_UNITS;
 constexpr int kPass = ABD_FCPRUNE_PASS_VARIANTS;
-
-inline unsigned grid_for(int64_t n, int64_t cap) {
-  int64_t b = (n + kT - 1) / kT;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
 
 // ---------------------------------------------------------------- hidden sums
 // sums[u] += sum_b d2[b][u]: block of 256 threads = 128 units x 2 row phases; a thread adds its rows
@@ -113,7 +110,8 @@ __global__ void __launch_bounds__(kT) fcprune_head_kernel(PruneArgs a, PruneMask
 }
 
 // one wave per variant of the pass: the rows' losses / hits summed in a fixed order (double; counts
-// <= B < 2^31 are exact in double) into the accumulators of variant v0 + blockIdx.x
+// <= B < 2^31 are exact in double) into the accumulators of variant v0 + blockIdx.x.  ablate.hip's
+// abl_reduce_kernel has this shape; that file compiles smallcnn.hip whole and keeps its own.
 __global__ void __launch_bounds__(64) fcprune_reduce_kernel(const float* __restrict__ rowloss,
                                                             const float* __restrict__ rowhit, int B, int v0,
                                                             double* __restrict__ loss_sum,
@@ -132,8 +130,6 @@ __global__ void __launch_bounds__(64) fcprune_reduce_kernel(const float* __restr
   }
 }
 
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ---------------------------------------------------------------- masked gradient + Adam
 struct MaskedAdamArgs {
   float* p;
@@ -143,34 +139,19 @@ struct MaskedAdamArgs {
   int64_t n;
   int64_t w_off, w_end;  // fc2.weight's elements [w_off, w_end) of the flat buffers, (K, 128) row-major
   const uint8_t* pruned;  // device uint8[128], nonzero = pruned
-  float omb1, beta2, omb2, step_size, bc2_sqrt, eps;
+  AdamConsts c;
 };
 
 // grads[fc2.weight[:, j]] <- 0 for every pruned unit j (the .grad torch leaves on weight_orig under
-// prune.custom_from_mask), then smallcnn.hip's adam_elem on the result.  adam_elem is compiled with
-// contraction on; its fused form is spelled out here with contraction off, so the store of the masked
-// gradient in between cannot make the compiler pick other products to fuse:
-//   m = fma(1 - beta1, g - m, m);  v = fma(g, (1 - beta2) g, beta2 v);  p = fma(-step, m / denom, p)
+// prune.custom_from_mask), then Adam on the result
 __global__ void __launch_bounds__(kT) masked_adam_kernel(MaskedAdamArgs a) {
-#pragma clang fp contract(off)
   for (int64_t i = blockIdx.x * (int64_t)kT + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kT) {
     float gi = a.g[i];
     if (i >= a.w_off && i < a.w_end && a.pruned[(i - a.w_off) & (kUnits - 1)]) {
       gi = 0.0f;
       a.g[i] = gi;
     }
-    const float m0 = a.m[i];
-    const float dm = gi - m0;
-    const float mi = __builtin_fmaf(a.omb1, dm, m0);
-    const float vb = a.v[i] * a.beta2;
-    const float og = a.omb2 * gi;
-    const float vi = __builtin_fmaf(gi, og, vb);
-    a.m[i] = mi;
-    a.v[i] = vi;
-    const float root = sqrtf(vi) / a.bc2_sqrt;
-    const float denom = root + a.eps;
-    const float q = mi / denom;
-    a.p[i] = __builtin_fmaf(-a.step_size, q, a.p[i]);
+    adam_elem_stored(gi, a.c, a.m, a.v, a.p, i);
   }
 }
 
@@ -200,8 +181,7 @@ int abd_smallcnn_hidden_sums(abd_cnn* net, const float* x, int64_t batch, const 
   ABD_CHECK(x && params && running && sums, ABD_E_INVALID, "NULL argument");
   ABD_CHECK(batch < (1LL << 31), ABD_E_INVALID, "batch too large");
   const size_t need = abd_smallcnn_workspace_bytes(net, batch);
-  ABD_CHECK(workspace && workspace_bytes >= need, ABD_E_WORKSPACE, "workspace too small (%zu < %zu)", workspace_bytes,
-            need);
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   const float* d2 = nullptr;
   if (int rc = baseline_forward(net, x, batch, params, running, workspace, need, stream, &d2)) return rc;
   hidden_sums_kernel<<<1, kT, 0, static_cast<hipStream_t>(stream)>>>(d2, (int)batch, sums);
@@ -226,8 +206,7 @@ int abd_smallcnn_fcprune_eval(abd_cnn* net, const float* x, int64_t batch, const
   const int64_t B = batch;
   const size_t cnn = abd_smallcnn_workspace_bytes(net, B);
   const size_t need = abd_smallcnn_fcprune_workspace_bytes(net, B, n_variants);
-  ABD_CHECK(workspace && workspace_bytes >= need, ABD_E_WORKSPACE, "workspace too small (%zu < %zu)", workspace_bytes,
-            need);
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   int64_t off[17];
   if (int rc = abd_smallcnn_param_offsets(net, off)) return rc;
   const int K = (int)(off[16] - off[15]);
@@ -275,41 +254,18 @@ int abd_smallcnn_pruned_finetune_step(abd_cnn* net, const abd_pruned_finetune_ar
                 a->pruned,
             ABD_E_INVALID, "NULL argument");
   const int64_t B = a->batch;
-  ABD_CHECK(B >= 1, ABD_E_INVALID, "fine-tuning step needs batch >= 1, got %lld", (long long)B);
-  ABD_CHECK(a->adam_step >= 1, ABD_E_INVALID, "adam_step is the 1-based step index, got %lld", (long long)a->adam_step);
+  if (int rc = check_adam_batch("fine-tuning step", B, a->adam_step)) return rc;
   const size_t need = abd_smallcnn_workspace_bytes(net, B);
-  ABD_CHECK(workspace && workspace_bytes >= need, ABD_E_WORKSPACE, "workspace too small (%zu < %zu)", workspace_bytes,
-            need);
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   int64_t off[17];
   if (int rc = abd_smallcnn_param_offsets(net, off)) return rc;
   ABD_CHECK((off[15] - off[14]) % kUnits == 0, ABD_E_UNSUPPORTED, "fc2 does not have %d inputs", kUnits);
   // 1. forward, loss, backward with the (already masked) parameters: the gradient of the effective weight
-  abd_train_args t{};
-  t.x = a->x;
-  t.labels = a->labels;
-  t.batch = B;
-  t.params = a->params;
-  t.grads = a->grads;
-  t.running = a->running;
-  t.num_batches_tracked = a->num_batches_tracked;
-  t.do_update = 0;
-  t.mask1_in = a->mask1_in;
-  t.mask2_in = a->mask2_in;
-  t.mask1_out = a->mask1_out;
-  t.mask2_out = a->mask2_out;
-  t.seed = a->seed;
-  t.counter = a->counter;
-  t.row_offset = a->row_offset;
-  t.logprobs_out = a->logprobs_out;
-  t.metrics = a->metrics;
-  t.grad_scale = 1.0f;
+  const abd_train_args t = no_update_args(*a);
   if (int rc = abd_smallcnn_train_step(net, &t, workspace, workspace_bytes, stream)) return rc;
-  // 2. + 3. the pruned columns' gradient zeroed and written back, Adam on it (abd_adam_f32's host constants)
-  const double bc1 = 1.0 - pow((double)a->beta1, (double)a->adam_step);
-  const double bc2 = 1.0 - pow((double)a->beta2, (double)a->adam_step);
+  // 2. + 3. the pruned columns' gradient zeroed and written back, Adam on it
   const MaskedAdamArgs ma{a->params, a->grads, a->exp_avg, a->exp_avg_sq, off[16], off[14], off[15], a->pruned,
-                          (float)(1.0 - (double)a->beta1), a->beta2, (float)(1.0 - (double)a->beta2),
-                          (float)((double)a->lr / bc1), (float)sqrt(bc2), a->eps};
+                          adam_consts(a->lr, a->beta1, a->beta2, a->eps, a->adam_step)};
   masked_adam_kernel<<<grid_for(off[16], 2048), kT, 0, static_cast<hipStream_t>(stream)>>>(ma);
   ABD_LAUNCH_CHECK();
   return ABD_OK;

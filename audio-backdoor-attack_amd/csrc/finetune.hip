@@ -9,6 +9,7 @@
 // 64-bit.  Reductions run in a fixed order (per-thread strided sums, wave butterfly, waves in index
 // order), no floating-point atomics, so equal inputs give bit-equal results.
 #include <cmath>
+#include <type_traits>
 
 #include "abd_common.h"
 
@@ -16,9 +17,10 @@ namespace {
 
 using abd::wave_sum_d;
 
-constexpr int kT = 256;
+// kT, kMaxSeg, round256, aligned16, segment_of, no_update_args, checks
+#include "defense_common.inc"
+
 constexpr int64_t kChunk = 4096;  // elements of one segment per block (16 per thread, 4 float4)
-constexpr int kMaxSeg = ABD_MAX_SEGMENTS;
 
 // Segment s is [off[s], off[s + 1]) and is covered by blocks [first[s], first[s + 1]), kChunk
 // elements each (the last one shorter): a block never straddles two segments.
@@ -52,12 +54,6 @@ int make_segtab(const int64_t* offsets, int n_seg, SegTab* t) {
   return ABD_OK;
 }
 
-__device__ __forceinline__ int segment_of(const SegTab& t, int bid) {
-  int s = 0;
-  while (s + 1 < t.n && t.first[s + 1] <= bid) ++s;
-  return s;
-}
-
 // A block's slice of its segment, split for 16-byte vector access relative to `ref`'s address:
 // [0, head) scalars, nvec float4 from head, then [tail, len) scalars.  head, len - tail <= 3.
 struct Slice {
@@ -83,7 +79,8 @@ __device__ __forceinline__ Slice slice_of(const SegTab& t, int s, int bid, const
   return c;
 }
 
-// Sum over the block in a fixed order; the result is valid in thread 0.
+// Sum over the block in a fixed order (wave butterflies, then the waves in index order); the result is
+// valid in thread 0.  Not nwc_corr.hip's block_sum, which adds in another order.
 __device__ __forceinline__ double block_sum_d(double v, double* sm) {
   v = wave_sum_d(v);
   const int wave = threadIdx.x >> 6;
@@ -100,7 +97,7 @@ __global__ void __launch_bounds__(kT) seg_sumsq_kernel(const float* __restrict__
                                                        double* __restrict__ part) {
   __shared__ double sm[kT / 64];
   const int bid = blockIdx.x, tid = threadIdx.x;
-  const int s = segment_of(t, bid);
+  const int s = segment_of(t.first, t.n, bid);
   const Slice c = slice_of(t, s, bid, buf, true);
   const float* q = buf + c.begin;
   double acc = 0.0;
@@ -147,7 +144,7 @@ __device__ __forceinline__ float perturb_one(float p, float g, float norm, float
 __global__ void __launch_bounds__(kT) perturb_kernel(const float* p, const float* g, const float* __restrict__ norms,
                                                      SegTab t, float r, float* out, int vec) {
   const int bid = blockIdx.x, tid = threadIdx.x;
-  const int s = segment_of(t, bid);
+  const int s = segment_of(t.first, t.n, bid);
   const Slice c = slice_of(t, s, bid, out, vec != 0);
   const float norm = norms[s];
   const float* pp = p + c.begin;
@@ -266,10 +263,6 @@ __global__ void __launch_bounds__(kT) ce_accuracy_kernel(const float* __restrict
   }
 }
 
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // The composite's workspace: the smallcnn workspace first, then the flat buffers it adds.
 struct RegWork {
   char* cnn;
@@ -286,7 +279,7 @@ RegWork reg_layout(const abd_cnn* net, int64_t B, const int64_t* off, char* base
   size_t o = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + o : nullptr;
-    o += align_up(bytes);
+    o += round256(bytes);
     return p;
   };
   w.cnn_bytes = abd_smallcnn_workspace_bytes(net, B);
@@ -318,8 +311,7 @@ int abd_segment_norms_f32(const float* buf, const int64_t* offsets, int n_seg, f
   if (int rc = make_segtab(offsets, n_seg, &t)) return rc;
   ABD_CHECK(buf && norms, ABD_E_INVALID, "NULL argument");
   const size_t need = (size_t)t.first[n_seg] * sizeof(double);
-  ABD_CHECK(workspace && workspace_bytes >= need, ABD_E_WORKSPACE, "workspace too small (%zu < %zu)", workspace_bytes,
-            need);
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   ABD_CHECK((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, ABD_E_INVALID, "workspace must be 8-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* part = static_cast<double*>(workspace);
@@ -379,7 +371,7 @@ int abd_smallcnn_finetune_reg_step(abd_cnn* net, const abd_finetune_reg_args* a,
   ABD_CHECK(net && a && a->x && a->labels && a->params && a->grads && a->running && a->loss_sum && a->correct,
             ABD_E_INVALID, "NULL argument");
   const int64_t B = a->batch;
-  ABD_CHECK(B >= 1, ABD_E_INVALID, "fine-tuning step needs batch >= 1, got %lld", (long long)B);
+  if (int rc = check_batch("fine-tuning step", B)) return rc;
   ABD_CHECK(a->momentum_buf != nullptr || a->momentum == 0.0f, ABD_E_INVALID, "momentum %g needs a momentum buffer",
             (double)a->momentum);
   int64_t off[17];
@@ -388,43 +380,21 @@ int abd_smallcnn_finetune_reg_step(abd_cnn* net, const abd_finetune_reg_args* a,
   const int K = (int)(off[16] - off[15]);
   ABD_CHECK((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, ABD_E_INVALID, "workspace must be 256-byte aligned");
   const RegWork w = reg_layout(net, B, off, static_cast<char*>(workspace));
-  ABD_CHECK(workspace && workspace_bytes >= w.bytes, ABD_E_WORKSPACE, "workspace too small (%zu < %zu)",
-            workspace_bytes, w.bytes);
+  if (int rc = check_workspace(workspace, workspace_bytes, w.bytes)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t lp_elems = (size_t)B * (size_t)K;
 
   // forwards 1 and 2 run on the reference's discarded copy: their BN statistics update a scratch copy
   ABD_HIP(hipMemcpyAsync(w.running, a->running, 320 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  abd_train_args t{};
-  t.x = a->x;
-  t.labels = a->labels;
-  t.batch = B;
-  t.running = w.running;
-  t.seed = a->seed;
-  t.row_offset = a->row_offset;
-  t.grad_scale = 1.0f;
   // 1. g1 at params
-  t.params = a->params;
-  t.grads = w.g1;
-  t.counter = a->counter;
-  t.mask1_in = a->mask1_in[0];
-  t.mask2_in = a->mask2_in[0];
-  t.mask1_out = a->mask1_out[0];
-  t.mask2_out = a->mask2_out[0];
-  t.logprobs_out = a->logprobs_out;
+  abd_train_args t = no_update_args(*a, 0, a->params, w.g1, w.running, nullptr, a->logprobs_out);
   if (int rc = abd_smallcnn_train_step(net, &t, w.cnn, w.cnn_bytes, stream)) return rc;
   // 2. the displaced parameters
   if (int rc = abd_segment_norms_f32(w.g1, off, 16, w.norms, w.part, w.part_bytes, stream)) return rc;
   if (int rc = abd_perturb_f32(a->params, w.g1, w.norms, off, 16, a->r, w.moved, stream)) return rc;
   // 3. g2 at the displaced parameters, into grads
-  t.params = w.moved;
-  t.grads = a->grads;
-  t.counter = a->counter + 1;
-  t.mask1_in = a->mask1_in[1];
-  t.mask2_in = a->mask2_in[1];
-  t.mask1_out = a->mask1_out[1];
-  t.mask2_out = a->mask2_out[1];
-  t.logprobs_out = a->logprobs_out ? a->logprobs_out + lp_elems : nullptr;
+  t = no_update_args(*a, 1, w.moved, a->grads, w.running, nullptr,
+                     a->logprobs_out ? a->logprobs_out + lp_elems : nullptr);
   if (int rc = abd_smallcnn_train_step(net, &t, w.cnn, w.cnn_bytes, stream)) return rc;
   // 4. SGD on the real parameters; grads <- (1 - alpha) g1 + alpha g2
   if (int rc = abd_sgd_f32(a->params, w.g1, a->grads, a->alpha, a->momentum_buf, a->momentum, a->lr, a->grads, n,
@@ -432,16 +402,7 @@ int abd_smallcnn_finetune_reg_step(abd_cnn* net, const abd_finetune_reg_args* a,
     return rc;
   // 5. the reference's third forward: the only one that touches the real BN buffers
   float* lp3 = a->logprobs_out ? a->logprobs_out + 2 * lp_elems : w.logp;
-  t.params = a->params;
-  t.grads = nullptr;
-  t.running = a->running;
-  t.num_batches_tracked = a->num_batches_tracked;
-  t.counter = a->counter + 2;
-  t.mask1_in = a->mask1_in[2];
-  t.mask2_in = a->mask2_in[2];
-  t.mask1_out = a->mask1_out[2];
-  t.mask2_out = a->mask2_out[2];
-  t.logprobs_out = lp3;
+  t = no_update_args(*a, 2, a->params, nullptr, a->running, a->num_batches_tracked, lp3);
   if (int rc = abd_smallcnn_forward(net, &t, 1, w.cnn, w.cnn_bytes, stream)) return rc;
   // 6. loss / accuracy of that forward
   ce_accuracy_kernel<<<1, kT, 0, s>>>(lp3, a->labels, B, K, a->loss_sum, a->correct);

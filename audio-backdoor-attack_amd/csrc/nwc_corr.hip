@@ -11,122 +11,39 @@
 // No atomics, no cross-block waits: the statistics kernel is a second launch, and its reductions walk LDS
 // in a fixed order, so equal inputs give bit-equal results.
 #include <cmath>
+#include <type_traits>
 
 #include "abd_common.h"
 
 namespace {
 
-constexpr int kT = 256;
-constexpr int kMaxSeg = ABD_MAX_SEGMENTS;
+// kT, RowTab / make_rowtab / row_abs_sums_body
+#include "defense_common.inc"
+
 constexpr int kMaxRows = ABD_MAX_REINIT_ROWS;
 
-// tsbd.hip's row table, its builder and absdiff_one, restated unchanged: abd_common.h belongs to the
-// benchmarked step's sources (scripts/traffic_json.py's csrc_sha1) and stays as it is.
-// Segment s: rows[s] rows of len[s] floats from element off[s] of the flat buffer.  Its rows are
-// rows rowfirst[s].. of the table, its values start at packfirst[s] of the packed |a - b| buffer.
-// In the row-sum kernel a row is handled by group[s] lanes (a power of two <= 64) and the segment by
-// blocks [first[s], first[s + 1]).
-struct RowTab {
-  int64_t off[kMaxSeg];
-  int64_t packfirst[kMaxSeg + 1];
-  int rows[kMaxSeg];
-  int len[kMaxSeg];
-  int rowfirst[kMaxSeg + 1];
-  int group[kMaxSeg];
-  int first[kMaxSeg + 1];
-  int n;
-};
-
-int make_rowtab(const abd_row_segment* table, int n_seg, RowTab* t) {
-  ABD_CHECK(table != nullptr, ABD_E_INVALID, "NULL row table");
-  ABD_CHECK(n_seg >= 1 && n_seg <= kMaxSeg, ABD_E_INVALID, "n_seg must be in [1, %d], got %d", kMaxSeg, n_seg);
-  int64_t rows = 0, packed = 0, blocks = 0, end = 0;
-  for (int s = 0; s < n_seg; ++s) {
-    const abd_row_segment& g = table[s];
-    ABD_CHECK(g.rows >= 1 && g.row_len >= 1, ABD_E_INVALID, "segment %d has empty rows (%lld rows of %lld)", s,
-              (long long)g.rows, (long long)g.row_len);
-    ABD_CHECK(g.rows < (1LL << 24) && g.row_len < (1LL << 24), ABD_E_INVALID, "segment %d is too large", s);
-    ABD_CHECK(g.offset >= end, ABD_E_INVALID, "segment %d starts at %lld, inside or before its predecessor (ends %lld)",
-              s, (long long)g.offset, (long long)end);
-    end = g.offset + g.rows * g.row_len;
-    int group = 1;
-    while (group < 64 && group < g.row_len) group <<= 1;
-    const int64_t rows_per_block = (int64_t)kT / group;
-    t->off[s] = g.offset;
-    t->packfirst[s] = packed;
-    t->rows[s] = (int)g.rows;
-    t->len[s] = (int)g.row_len;
-    t->rowfirst[s] = (int)rows;
-    t->group[s] = group;
-    t->first[s] = (int)blocks;
-    rows += g.rows;
-    packed += g.rows * g.row_len;
-    blocks += (g.rows + rows_per_block - 1) / rows_per_block;
-    ABD_CHECK(rows < (1LL << 30) && packed < (1LL << 40) && blocks < (1LL << 30), ABD_E_INVALID, "row table too large");
-  }
-  for (int s = n_seg; s < kMaxSeg; ++s) {
-    t->off[s] = end;
-    t->rows[s] = t->len[s] = 0;
-    t->group[s] = 1;
-  }
-  for (int s = n_seg; s <= kMaxSeg; ++s) {
-    t->packfirst[s] = packed;
-    t->rowfirst[s] = (int)rows;
-    t->first[s] = (int)blocks;
-  }
-  t->n = n_seg;
-  return ABD_OK;
-}
-
-// |a - b|: one fp32 subtraction and a sign clear (torch's (a - b).abs())
-__device__ __forceinline__ float absdiff_one(const float* a, const float* b, int64_t i) {
-  const float d = b ? a[i] - b[i] : a[i];
-  return __builtin_fabsf(d);
-}
-
-// row_abs_sums_kernel (tsbd.hip) for two buffers against one original: the same lane groups, the same
-// per-lane strided double sums and butterfly, hence the same fp32 row sums bit for bit.
+// tsbd.hip's row_abs_sums_kernel for two buffers against one original: the one shared row body, hence the
+// same fp32 row sums bit for bit; the double sums are kept before that rounding.
 __global__ void __launch_bounds__(kT) nwc_pair_rows_kernel(const float* __restrict__ orig,
                                                            const float* __restrict__ pa,
                                                            const float* __restrict__ pb, RowTab t,
                                                            float* __restrict__ absdiff_a, float* __restrict__ absdiff_b,
                                                            float* __restrict__ sums32_a, float* __restrict__ sums32_b,
                                                            double* __restrict__ sums64, int total_rows) {
-  const int bid = blockIdx.x, tid = threadIdx.x;
-  int s = 0;
-  while (s + 1 < t.n && t.first[s + 1] <= bid) ++s;
-  const int group = t.group[s], len = t.len[s];
-  const int row = (bid - t.first[s]) * (kT / group) + tid / group;
-  const int j = tid & (group - 1);
-  const bool live = row < t.rows[s];
-  double acc_a = 0.0, acc_b = 0.0;
-  if (live) {
-    const int64_t src = t.off[s] + (int64_t)row * len;
-    const int64_t dst = t.packfirst[s] + (int64_t)row * len;
-    for (int e = j; e < len; e += group) {
-      const float va = absdiff_one(pa, orig, src + e);
-      const float vb = absdiff_one(pb, orig, src + e);
-      if (absdiff_a) absdiff_a[dst + e] = va;
-      if (absdiff_b) absdiff_b[dst + e] = vb;
-      acc_a += (double)va;
-      acc_b += (double)vb;
-    }
-  }
-  // lanes of a group share a wave (group divides 64); dead rows carry zeros and write nothing
-  for (int o = group >> 1; o > 0; o >>= 1) {
-    acc_a += __shfl_xor(acc_a, o, 64);
-    acc_b += __shfl_xor(acc_b, o, 64);
-  }
-  if (live && j == 0) {
-    const int r = t.rowfirst[s] + row;
-    sums32_a[r] = (float)acc_a;
-    sums32_b[r] = (float)acc_b;
-    sums64[r] = acc_a;
-    sums64[total_rows + r] = acc_b;
+  const float* const ps[2] = {pa, pb};
+  float* const ad[2] = {absdiff_a, absdiff_b};
+  double acc[2];
+  const int r = row_abs_sums_body<2>(t, ps, orig, ad, acc);
+  if (r >= 0) {
+    sums32_a[r] = (float)acc[0];
+    sums32_b[r] = (float)acc[1];
+    sums64[r] = acc[0];
+    sums64[total_rows + r] = acc[1];
   }
 }
 
-// Block-wide sum in a fixed order: thread i's value into LDS slot i, then halving strides.
+// Block-wide sum in a fixed order: thread i's value into LDS slot i, then halving strides.  Not
+// finetune.hip's block_sum_d, which adds in another order.
 __device__ __forceinline__ double block_sum(double v, double* sm) {
   const int tid = threadIdx.x;
   __syncthreads();  // the previous reduction's readers are done with sm

@@ -121,6 +121,13 @@ def _flat_state(model, device):
     return params, running
 
 
+def _eval_state(model, device):
+    """(params, running, K, precision): what the eval-side ops take of a model."""
+    params, running = _flat_state(model, device)
+    K = int(model.state_dict()["fc2.weight"].shape[0])
+    return params, running, K, getattr(model, "gemm_precision", "f32split")
+
+
 def _geometry(H0, W0):
     H1, W1p = H0 - 1, (W0 - 1) // 3
     H2, W2 = H1 - 1, W1p - 1
@@ -155,9 +162,7 @@ def ablation_sweep(model, x, y, masks, kind="conv", batch_size=256, variants_per
     masks = torch.as_tensor(masks).detach().to("cpu", torch.uint8).contiguous()
     V, N = int(masks.shape[0]), int(x.shape[0])
     dev = x.device
-    params, running = _flat_state(model, dev)
-    K = int(model.state_dict()["fc2.weight"].shape[0])
-    prec = getattr(model, "gemm_precision", "f32split")
+    params, running, K, prec = _eval_state(model, dev)
     y = y.to(torch.int64)
     bounds = batch_bounds(N, int(batch_size))
     loss_sums = torch.zeros((max(len(bounds), 1), V), dtype=torch.float64, device=dev)
@@ -203,16 +208,30 @@ def epoch_order(n: int, order):
     return o
 
 
-def _epoch_batches(x, y, batch_size, order):
-    """[(x_b, y_b)] device batches in the epoch's order: views when sequential, gathers under a permutation."""
+def _batches(x, y, batch_size, order, first_only=False):
+    """The device batches of a set in the epoch's order: [x_b] without y, else [(x_b, y_b)] with int64 labels;
+    views when sequential, gathers under a permutation.  first_only: the first batch alone."""
     N = int(x.shape[0])
     o = epoch_order(N, order)
+    bounds = batch_bounds(N, int(batch_size))[:1 if first_only else None]
+    idx = None if o is None else torch.from_numpy(o).to(x.device)
+
+    def rows(t, s, e):
+        return t[s:e] if idx is None else t.index_select(0, idx[s:e])
+    if y is None:
+        return [rows(x, s, e) for s, e in bounds]
     y = y.to(torch.int64)
-    bounds = batch_bounds(N, int(batch_size))
-    if o is None:
-        return [(x[s:e], y[s:e]) for s, e in bounds]
-    idx = torch.from_numpy(o).to(x.device)
-    return [(x.index_select(0, idx[s:e]), y.index_select(0, idx[s:e])) for s, e in bounds]
+    return [(rows(x, s, e), rows(y, s, e)) for s, e in bounds]
+
+
+def _epoch_batches(x, y, batch_size, order):
+    """[(x_b, y_b)] device batches in the epoch's order."""
+    return _batches(x, y, batch_size, order)
+
+
+def _x_batches(x, batch_size, order, first_only=False):
+    """[x_b]: _epoch_batches without labels."""
+    return _batches(x, None, batch_size, order, first_only)
 
 
 def _check_finetune_inputs(model, x, y, what):
@@ -345,6 +364,29 @@ def _adam_binding(model, optimizer, what):
     return T.AdamBinding(model, optimizer)
 
 
+def _adam_epoch(model, eng, adam, batches, own, masks=None):
+    """The batch loop that unlearn_epoch and pruned_finetune_epoch share, and what follows it.  Per batch, in this
+    order: the dropout masks (masks[i], else one draw of model.step_masks), adam.step += 1, the op, model._step
+    += 1.  own() -> (the op, its tensor argument after metrics, its arguments between counter and mask1_in).
+    Then the optimizer's torch state and the parameters' .grad; returns read_metrics' numbers."""
+    from . import training as T
+    from .models import dropout_seed
+    dev = eng.device
+    metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
+    for i, (xb, yb) in enumerate(batches):
+        hm = masks[i] if masks is not None else model.step_masks(int(xb.shape[0]), dev)
+        op, tensor, after = own()
+        adam.step += 1
+        op(xb.contiguous(), yb.contiguous(), eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, eng.running, eng.nbt,
+           metrics, tensor, None, None, eng.K, adam.step, adam.lr, adam.betas[0], adam.betas[1], adam.eps,
+           dropout_seed(dev, model), model._step, *after, hm[0] if hm is not None else None,
+           hm[1] if hm is not None else None, model.gemm_precision)
+        model._step += 1
+    adam.sync_torch_state()
+    T.expose_grads(model)
+    return T.read_metrics(metrics)
+
+
 def unlearn_epoch(model, x, y, optimizer, record_layer="conv3.weight", batch_size=256, order=None, whole_epoch=False):
     """One call of train_unlearning (tsbd.py:108-138, correlation_analysis.py:41-71) on device-resident
     (x, y): gradient ascent on the CrossEntropyLoss with torch.optim.Adam, one
@@ -357,8 +399,7 @@ def unlearn_epoch(model, x, y, optimizer, record_layer="conv3.weight", batch_siz
     batches' rows.  record_layer None records nothing (correlation_analysis.py's variant): the two
     gradient-norm results are then None.  The parameters' .grad are views of the last batch's gradient
     of -loss, as ``(-loss).backward()`` leaves them."""
-    from . import ops, training as T  # noqa: F401  (registers torch.ops.abd)
-    from .models import dropout_seed
+    from . import ops  # noqa: F401  (registers torch.ops.abd)
     _check_finetune_inputs(model, x, y, "unlearn_epoch")
     model.train()
     dev = x.device
@@ -372,22 +413,12 @@ def unlearn_epoch(model, x, y, optimizer, record_layer="conv3.weight", batch_siz
         p = d[record_layer]
         record = [eng.offsets[PARAM_ORDER.index(record_layer)], int(p.shape[0]), int(p.numel() // p.shape[0])]
     batches = _epoch_batches(x, y, batch_size, order)
-    metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
     norms = []
-    for xb, yb in batches if whole_epoch else batches[:1]:
-        hm = model.step_masks(int(xb.shape[0]), dev)
-        row = torch.empty(record[1], dtype=torch.float32, device=dev) if record else None
-        adam.step += 1
-        torch.ops.abd.smallcnn_unlearn_step(
-            xb.contiguous(), yb.contiguous(), eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, eng.running, eng.nbt,
-            metrics, row, None, None, eng.K, adam.step, adam.lr, adam.betas[0], adam.betas[1], adam.eps,
-            dropout_seed(dev, model), model._step, record, hm[0] if hm is not None else None,
-            hm[1] if hm is not None else None, model.gemm_precision)
-        model._step += 1
-        norms.append(row)
-    adam.sync_torch_state()
-    T.expose_grads(model)
-    loss_sum, _, hit, _, _, _ = T.read_metrics(metrics)
+
+    def own():
+        norms.append(torch.empty(record[1], dtype=torch.float32, device=dev) if record else None)
+        return torch.ops.abd.smallcnn_unlearn_step, norms[-1], (record,)
+    loss_sum, _, hit, _, _, _ = _adam_epoch(model, eng, adam, batches if whole_epoch else batches[:1], own)
     loss, acc = loss_sum / len(batches), float(hit) / int(x.shape[0])
     if record is None:
         return loss, acc, None, None
@@ -535,9 +566,7 @@ def reinit_sweep(model, clean_x, clean_y, bd_x, bd_y, bd_indicator, ranked, absd
         L.require_device(t, f"reinit_sweep {what}")
     dev = clean_x.device
     params, _, _ = reinit_models(model, ranked, absdiff, ratios, wratio)
-    _, running = _flat_state(model, dev)
-    K = int(model.state_dict()["fc2.weight"].shape[0])
-    prec = getattr(model, "gemm_precision", "f32split")
+    _, running, K, prec = _eval_state(model, dev)
     clean_y, bd_y, bd_indicator = clean_y.to(torch.int64), bd_y.to(torch.int64), bd_indicator.to(torch.int64)
     return [_test_numbers(params[v], running, K, prec, clean_x, clean_y, bd_x, bd_y, bd_indicator, batch_size)
             for v in range(len(ratios))]
@@ -585,19 +614,11 @@ def unlearn_run(model, x, y, optimizer, n_steps, batch_size=256, order=None, mas
     model.train()
     dev = x.device
     N = int(x.shape[0])
-    bounds = batch_bounds(N, int(batch_size))
-    s, e = bounds[0]
-    o = epoch_order(N, order)
-    y = y.to(torch.int64)
-    if o is None:
-        xb, yb = x[s:e], y[s:e]
-    else:
-        idx = torch.from_numpy(o[s:e]).to(dev)
-        xb, yb = x.index_select(0, idx), y.index_select(0, idx)
-    xb, yb = xb.contiguous(), yb.contiguous()
+    n_batches = len(batch_bounds(N, int(batch_size)))
+    xb, yb = (t.contiguous() for t in _batches(x, y, batch_size, order, first_only=True)[0])
     eng = model.engine(xb)
     adam = _adam_binding(model, optimizer, "unlearn_run")
-    B = e - s
+    B = int(xb.shape[0])
     if masks is None and getattr(model, "dropout_source", "device") == "torch_cpu":
         drawn = [model.step_masks(B, dev) for _ in range(n_steps)]
         masks = torch.stack([d[0] for d in drawn]), torch.stack([d[1] for d in drawn])
@@ -613,7 +634,7 @@ def unlearn_run(model, x, y, optimizer, n_steps, batch_size=256, order=None, mas
     T.expose_grads(model)
     words = metrics.cpu().numpy()
     loss_sums = np.ascontiguousarray(words[:, 0]).view(np.float64)
-    return [float(v) / len(bounds) for v in loss_sums], [float(h) / N for h in words[:, 2]]
+    return [float(v) / n_batches for v in loss_sums], [float(h) / N for h in words[:, 2]]
 
 
 def correlation_stats(clean_scores, bd_scores):
@@ -726,16 +747,6 @@ def save_correlation_outputs(result, directory):
 FP_UNITS = L.FCPRUNE_UNITS
 
 
-def _x_batches(x, batch_size, order):
-    N = int(x.shape[0])
-    o = epoch_order(N, order)
-    bounds = batch_bounds(N, int(batch_size))
-    if o is None:
-        return [x[s:e] for s, e in bounds]
-    idx = torch.from_numpy(o).to(x.device)
-    return [x.index_select(0, idx[s:e]) for s, e in bounds]
-
-
 def _check_eval_input(x, what):
     L.require_device(x, f"{what} input")
     if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
@@ -755,12 +766,9 @@ def hidden_activation(model, x, batch_size=256, order=None, first_batch_only=Tru
     if x.shape[0] == 0:
         raise ValueError("hidden_activation needs at least one row")
     dev = x.device
-    params, running = _flat_state(model, dev)
-    K = int(model.state_dict()["fc2.weight"].shape[0])
-    prec = getattr(model, "gemm_precision", "f32split")
+    params, running, K, prec = _eval_state(model, dev)
     sums = torch.zeros(FP_UNITS, dtype=torch.float64, device=dev)
-    batches = _x_batches(x, batch_size, order)
-    for xb in batches[:1] if first_batch_only else batches:
+    for xb in _x_batches(x, batch_size, order, first_only=first_batch_only):
         torch.ops.abd.smallcnn_hidden_sums(xb.contiguous(), params, running, sums, K, prec)
     return (sums / float(x.shape[0])).to(torch.float32).cpu()
 
@@ -802,9 +810,7 @@ def fc_prune_sweep(model, x, y, masks, batch_size=256):
     masks = torch.as_tensor(masks).detach().to("cpu", torch.uint8).contiguous()
     V, N = int(masks.shape[0]), int(x.shape[0])
     dev = x.device
-    params, running = _flat_state(model, dev)
-    K = int(model.state_dict()["fc2.weight"].shape[0])
-    prec = getattr(model, "gemm_precision", "f32split")
+    params, running, K, prec = _eval_state(model, dev)
     y = y.to(torch.int64)
     bounds = batch_bounds(N, int(batch_size))
     loss_sums = torch.zeros((max(len(bounds), 1), V), dtype=torch.float64, device=dev)
@@ -844,8 +850,7 @@ def pruned_finetune_epoch(model, x, y, optimizer, unit_mask, batch_size=256, ord
     optional dropout keep-masks per batch [(mask1 (B, flat), mask2 (B, 128))] uint8 device tensors (default:
     the model's dropout source).  Returns (loss, acc): the sum of the batch-mean losses over the number of
     batches and correct predictions over samples."""
-    from . import ops, training as T  # noqa: F401  (registers torch.ops.abd)
-    from .models import dropout_seed
+    from . import ops  # noqa: F401  (registers torch.ops.abd)
     _check_finetune_inputs(model, x, y, "pruned_finetune_epoch")
     unit = torch.as_tensor(unit_mask).detach().reshape(-1).to("cpu").ne(0)
     if unit.numel() != FP_UNITS:
@@ -860,19 +865,8 @@ def pruned_finetune_epoch(model, x, y, optimizer, unit_mask, batch_size=256, ord
     batches = _epoch_batches(x, y, batch_size, order)
     if masks is not None and len(masks) != len(batches):
         raise ValueError("masks needs one (mask1, mask2) pair per batch")
-    metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
-    for i, (xb, yb) in enumerate(batches):
-        hm = masks[i] if masks is not None else model.step_masks(int(xb.shape[0]), dev)
-        adam.step += 1
-        torch.ops.abd.smallcnn_pruned_finetune_step(
-            xb.contiguous(), yb.contiguous(), eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, eng.running, eng.nbt,
-            metrics, pruned, None, None, eng.K, adam.step, adam.lr, adam.betas[0], adam.betas[1], adam.eps,
-            dropout_seed(dev, model), model._step, hm[0] if hm is not None else None,
-            hm[1] if hm is not None else None, model.gemm_precision)
-        model._step += 1
-    adam.sync_torch_state()
-    T.expose_grads(model)
-    loss_sum, total, hit, _, _, _ = T.read_metrics(metrics)
+    loss_sum, total, hit, _, _, _ = _adam_epoch(
+        model, eng, adam, batches, lambda: (torch.ops.abd.smallcnn_pruned_finetune_step, pruned, ()), masks)
     return loss_sum / len(batches), hit / total
 
 

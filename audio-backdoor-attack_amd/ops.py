@@ -242,6 +242,68 @@ def _(params, grads, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps):
     return None
 
 
+# --------------------------------------------------------------------------- the defences' step ops
+_MASK_FIELDS = ("mask1_in", "mask2_in", "mask1_out", "mask2_out")
+
+
+def _check_masks(masks, B, flat, lead=()):
+    """masks = (mask1_in, mask2_in, mask1_out, mask2_out), each None or a uint8 device tensor (*lead, B, flat) /
+    (*lead, B, 128); the in and the out masks come in pairs."""
+    if (masks[0] is None) != (masks[1] is None) or (masks[2] is None) != (masks[3] is None):
+        raise L.AbdError("dropout masks come in pairs")
+    for m, cols, what in zip(masks, (flat, 128, flat, 128), _MASK_FIELDS):
+        if m is None:
+            continue
+        L.require_device(m, what)
+        shape = (*lead, B, cols)
+        if m.dtype != torch.uint8 or tuple(m.shape) != shape:
+            raise L.AbdError(f"{what} must be uint8 {shape}, got {tuple(m.shape)}")
+
+
+def _defence_step(name, a, x, labels, state, num_classes, precision, seed, counter, row_offset, masks, adam=None,
+                  lead=(), out_lead=(), workspace=None, extra=()):
+    """What the step ops of ft_reg, TSBD, the correlation analysis and fine-pruning share; returns the log-probs
+    (*out_lead, B, K).  a: abd_smallcnn_<name>'s argument struct with the op's own fields set; state: {field:
+    flat device buffer}, written into the fields of those names; adam: (adam_step, lr, beta1, beta2, eps) for the
+    structs that carry them; masks: see _check_masks -- a struct with one mask pointer per pass (FinetuneRegArgs)
+    gets the lead slices, any other the tensor's start; workspace: the <w> of abd_smallcnn_<w>_workspace_bytes;
+    extra: the arguments between the struct and the workspace."""
+    L.require_device(x, "smallcnn input")
+    L.require_device(labels, "labels")
+    for what, t in state.items():
+        L.require_device(t, what)
+    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    h = _net(H0, W0, num_classes, precision)
+    flat = L.lib().abd_smallcnn_flat_features(h)
+    if labels.dtype != torch.int64 or labels.numel() != B:
+        raise L.AbdError("labels must be int64, one per batch row")
+    _check_masks(masks, B, flat, lead)
+    for m, cols, what in zip(masks, (flat, 128, flat, 128), _MASK_FIELDS):
+        field = getattr(a, what)
+        if not isinstance(field, C.Array):
+            setattr(a, what, _ptr(m))
+        elif m is not None:
+            for k in range(len(field)):
+                field[k] = m.data_ptr() + k * B * cols
+    out = torch.empty((*out_lead, B, int(num_classes)), dtype=torch.float32, device=x.device)
+    a.x, a.labels, a.batch = x.data_ptr(), labels.data_ptr(), B
+    for what, t in state.items():
+        setattr(a, what, t.data_ptr())
+    if adam is not None:
+        a.adam_step, a.lr, a.beta1, a.beta2, a.eps = int(adam[0]), *(float(v) for v in adam[1:])
+    a.seed, a.counter, a.row_offset = int(seed), int(counter), int(row_offset)
+    a.logprobs_out = out.data_ptr()
+    ws = _ws(getattr(L.lib(), f"abd_smallcnn_{workspace}_workspace_bytes")(h, B), x.device)
+    L.check(getattr(L.lib(), f"abd_smallcnn_{name}")(h, C.byref(a), *extra, ws.data_ptr(), ws.numel(),
+                                                     L.stream_ptr(x.device)), f"abd_smallcnn_{name}")
+    return out
+
+
+def _adam_state(params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics):
+    return dict(params=params, grads=grads, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq, running=running,
+                num_batches_tracked=num_batches_tracked, metrics=metrics)
+
+
 # --------------------------------------------------------------------------- fine-tuning (ft_reg.py)
 def _offsets(offsets):
     """Segment offsets as the C ABI's host int64 array (validated by the library)."""
@@ -333,41 +395,18 @@ def smallcnn_finetune_reg_step(x: Tensor, labels: Tensor, params: Tensor, grads:
     left holding (1 - alpha) g1 + alpha g2, loss_sum (float64[1]) += the post-update batch-mean loss, correct
     (int64[1]) += its hits.  mask*_in / mask*_out are (3, B, flat) and (3, B, 128) uint8, one slice per forward;
     without mask*_in the masks come from (seed, counter), (seed, counter + 1), (seed, counter + 2)."""
-    L.require_device(x, "smallcnn input")
-    for t, what in ((labels, "labels"), (params, "params"), (grads, "grads"), (running, "running"),
-                    (num_batches_tracked, "num_batches_tracked"), (loss_sum, "loss_sum"), (correct, "correct")):
+    for t, what in ((loss_sum, "loss_sum"), (correct, "correct")):
         L.require_device(t, what)
-    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    h = _net(H0, W0, num_classes, precision)
-    flat = L.lib().abd_smallcnn_flat_features(h)
-    if labels.dtype != torch.int64 or labels.numel() != B:
-        raise L.AbdError("labels must be int64, one per batch row")
     if loss_sum.dtype != torch.float64 or correct.dtype != torch.int64 or not loss_sum.numel() or not correct.numel():
         raise L.AbdError("loss_sum (float64) and correct (int64) need one entry each")
-    if (mask1_in is None) != (mask2_in is None) or (mask1_out is None) != (mask2_out is None):
-        raise L.AbdError("dropout masks come in pairs")
     a = L.FinetuneRegArgs()
-    for m, cols, what in ((mask1_in, flat, "mask1_in"), (mask2_in, 128, "mask2_in"), (mask1_out, flat, "mask1_out"),
-                          (mask2_out, 128, "mask2_out")):
-        if m is None:
-            continue
-        L.require_device(m, what)
-        if m.dtype != torch.uint8 or tuple(m.shape) != (3, B, cols):
-            raise L.AbdError(f"{what} must be uint8 (3, {B}, {cols}), got {tuple(m.shape)}")
-        for k in range(3):
-            getattr(a, what)[k] = m.data_ptr() + k * B * cols
-    out = torch.empty((3, B, int(num_classes)), dtype=torch.float32, device=x.device)
-    a.x, a.labels, a.batch = x.data_ptr(), labels.data_ptr(), B
-    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
-    a.num_batches_tracked = num_batches_tracked.data_ptr()
-    a.seed, a.counter, a.row_offset = int(seed), int(counter), int(row_offset)
     a.r, a.alpha, a.lr, a.momentum = float(r), float(alpha), float(lr), float(momentum)
     a.momentum_buf = _ptr(momentum_buf)
-    a.logprobs_out, a.loss_sum, a.correct = out.data_ptr(), loss_sum.data_ptr(), correct.data_ptr()
-    ws = _ws(L.lib().abd_smallcnn_finetune_reg_workspace_bytes(h, B), x.device)
-    L.check(L.lib().abd_smallcnn_finetune_reg_step(h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
-            "abd_smallcnn_finetune_reg_step")
-    return out
+    a.loss_sum, a.correct = loss_sum.data_ptr(), correct.data_ptr()
+    state = dict(params=params, grads=grads, running=running, num_batches_tracked=num_batches_tracked)
+    return _defence_step("finetune_reg_step", a, x, labels, state, num_classes, precision, seed, counter, row_offset,
+                         (mask1_in, mask2_in, mask1_out, mask2_out), lead=(3,), out_lead=(3,),
+                         workspace="finetune_reg")
 
 
 @smallcnn_finetune_reg_step.register_fake
@@ -396,6 +435,18 @@ def _table_extent(vals):
     return rows, packed, end
 
 
+def _checked_row_table(table, numel=None):
+    """_row_table plus what its callers ask of it: no negative entry and, with numel given, an end inside a buffer
+    of that many elements.  Returns (C array, n_seg, total rows, packed values, one past the last element)."""
+    arr, n_seg, vals = _row_table(table)
+    if min(vals) < 0:
+        raise L.AbdError("row table entries must not be negative")
+    rows, packed, end = _table_extent(vals)
+    if numel is not None and end > numel:
+        raise L.AbdError("row table reaches past the buffer")
+    return arr, n_seg, rows, packed, end
+
+
 @torch.library.custom_op("abd::row_abs_sums", mutates_args=())
 def row_abs_sums(a: Tensor, b: Optional[Tensor], table: list[int], want_absdiff: bool = True) -> tuple[Tensor, Tensor]:
     """(absdiff, row_sums) of a row table (flat (offset, rows, row_len) triples) over flat fp32 buffers:
@@ -409,12 +460,7 @@ def row_abs_sums(a: Tensor, b: Optional[Tensor], table: list[int], want_absdiff:
         L.require_device(b, "row_abs_sums b")
         if b.dtype != torch.float32 or b.numel() != a.numel():
             raise L.AbdError("row_abs_sums: b must be float32 with a's element count")
-    arr, n_seg, vals = _row_table(table)
-    if min(vals) < 0:
-        raise L.AbdError("row table entries must not be negative")
-    rows, packed, end = _table_extent(vals)
-    if end > a.numel():
-        raise L.AbdError("row table reaches past the buffer")
+    arr, n_seg, rows, packed, _ = _checked_row_table(table, a.numel())
     absdiff = torch.empty(packed if want_absdiff else 0, dtype=torch.float32, device=a.device)
     sums = torch.empty(rows, dtype=torch.float32, device=a.device)
     L.check(L.lib().abd_row_abs_sums_f32(a.data_ptr(), _ptr(b), arr, n_seg, absdiff.data_ptr() if want_absdiff else None,
@@ -442,24 +488,6 @@ def smallcnn_unlearn_step(x: Tensor, labels: Tensor, params: Tensor, grads: Tens
     A no-update train step (metrics += the positive loss and the hits, BN buffers advance once), then grads
     <- -grads and torch.optim.Adam (step index adam_step >= 1) on it.  record = [offset, rows, row_len] of the
     record layer inside the flat buffers: record_abs_sums (float32[rows]) receives its per-row |grad| sums."""
-    L.require_device(x, "smallcnn input")
-    for t, what in ((labels, "labels"), (params, "params"), (grads, "grads"), (exp_avg, "exp_avg"),
-                    (exp_avg_sq, "exp_avg_sq"), (running, "running"), (num_batches_tracked, "num_batches_tracked"),
-                    (metrics, "metrics")):
-        L.require_device(t, what)
-    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    h = _net(H0, W0, num_classes, precision)
-    flat = L.lib().abd_smallcnn_flat_features(h)
-    if labels.dtype != torch.int64 or labels.numel() != B:
-        raise L.AbdError("labels must be int64, one per batch row")
-    if (mask1_in is None) != (mask2_in is None) or (mask1_out is None) != (mask2_out is None):
-        raise L.AbdError("dropout masks come in pairs")
-    for m, cols, what in ((mask1_in, flat, "mask1_in"), (mask2_in, 128, "mask2_in"), (mask1_out, flat, "mask1_out"),
-                          (mask2_out, 128, "mask2_out")):
-        if m is not None:
-            L.require_device(m, what)
-            if m.dtype != torch.uint8 or tuple(m.shape) != (B, cols):
-                raise L.AbdError(f"{what} must be uint8 ({B}, {cols}), got {tuple(m.shape)}")
     a = L.UnlearnArgs()
     if record is not None:
         if len(record) != 3 or record_abs_sums is None:
@@ -469,19 +497,10 @@ def smallcnn_unlearn_step(x: Tensor, labels: Tensor, params: Tensor, grads: Tens
             raise L.AbdError("record_abs_sums must be float32 with one entry per record row")
         a.record_offset, a.record_rows, a.record_row_len = (int(v) for v in record)
         a.record_abs_sums = record_abs_sums.data_ptr()
-    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
-    a.x, a.labels, a.batch = x.data_ptr(), labels.data_ptr(), B
-    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
-    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
-    a.num_batches_tracked = num_batches_tracked.data_ptr()
-    a.adam_step, a.lr, a.beta1, a.beta2, a.eps = int(adam_step), float(lr), float(beta1), float(beta2), float(eps)
-    a.seed, a.counter, a.row_offset = int(seed), int(counter), int(row_offset)
-    a.mask1_in, a.mask2_in, a.mask1_out, a.mask2_out = _ptr(mask1_in), _ptr(mask2_in), _ptr(mask1_out), _ptr(mask2_out)
-    a.logprobs_out, a.metrics = out.data_ptr(), metrics.data_ptr()
-    ws = _ws(L.lib().abd_smallcnn_unlearn_workspace_bytes(h, B), x.device)
-    L.check(L.lib().abd_smallcnn_unlearn_step(h, C.byref(a), ws.data_ptr(), ws.numel(), L.stream_ptr(x.device)),
-            "abd_smallcnn_unlearn_step")
-    return out
+    return _defence_step("unlearn_step", a, x, labels,
+                         _adam_state(params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics),
+                         num_classes, precision, seed, counter, row_offset, (mask1_in, mask2_in, mask1_out, mask2_out),
+                         adam=(adam_step, lr, beta1, beta2, eps), workspace="unlearn")
 
 
 @smallcnn_unlearn_step.register_fake
@@ -502,10 +521,7 @@ def reinit_weights(params: Tensor, absdiff: Tensor, table: list[int], row_select
     L.require_device(absdiff, "absdiff")
     if params.dtype != torch.float32 or absdiff.dtype != torch.float32:
         raise L.AbdError("reinit_weights expects float32")
-    arr, n_seg, vals = _row_table(table)
-    if min(vals) < 0:
-        raise L.AbdError("row table entries must not be negative")
-    rows, packed, end = _table_extent(vals)
+    arr, n_seg, rows, packed, end = _checked_row_table(table)
     sel = row_select.detach().to("cpu", torch.uint8).contiguous()
     V = len(k)
     if sel.dim() != 2 or tuple(sel.shape) != (V, rows):
@@ -544,43 +560,16 @@ def smallcnn_unlearn_run(x: Tensor, labels: Tensor, params: Tensor, grads: Tenso
     returns the last step's log-probs (B, K).  Step i is abd::smallcnn_unlearn_step with adam_step + i and
     counter + i and no record layer, bit for bit.  metrics is int64 (n_steps, 8), zeroed by the caller: row i
     holds step i's loss and hits.  The masks, when given, are (n_steps, B, flat) and (n_steps, B, 128) uint8."""
-    L.require_device(x, "smallcnn input")
-    for t, what in ((labels, "labels"), (params, "params"), (grads, "grads"), (exp_avg, "exp_avg"),
-                    (exp_avg_sq, "exp_avg_sq"), (running, "running"), (num_batches_tracked, "num_batches_tracked"),
-                    (metrics, "metrics")):
-        L.require_device(t, what)
     n_steps = int(n_steps)
     if n_steps < 1:
         raise L.AbdError(f"smallcnn_unlearn_run needs n_steps >= 1, got {n_steps}")
-    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    h = _net(H0, W0, num_classes, precision)
-    flat = L.lib().abd_smallcnn_flat_features(h)
-    if labels.dtype != torch.int64 or labels.numel() != B:
-        raise L.AbdError("labels must be int64, one per batch row")
     if metrics.dtype != torch.int64 or tuple(metrics.shape) != (n_steps, L.METRICS_WORDS):
         raise L.AbdError(f"metrics must be int64 ({n_steps}, {L.METRICS_WORDS}), got {tuple(metrics.shape)}")
-    if (mask1_in is None) != (mask2_in is None) or (mask1_out is None) != (mask2_out is None):
-        raise L.AbdError("dropout masks come in pairs")
-    for m, cols, what in ((mask1_in, flat, "mask1_in"), (mask2_in, 128, "mask2_in"), (mask1_out, flat, "mask1_out"),
-                          (mask2_out, 128, "mask2_out")):
-        if m is not None:
-            L.require_device(m, what)
-            if m.dtype != torch.uint8 or tuple(m.shape) != (n_steps, B, cols):
-                raise L.AbdError(f"{what} must be uint8 ({n_steps}, {B}, {cols}), got {tuple(m.shape)}")
-    a = L.UnlearnArgs()
-    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
-    a.x, a.labels, a.batch = x.data_ptr(), labels.data_ptr(), B
-    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
-    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
-    a.num_batches_tracked = num_batches_tracked.data_ptr()
-    a.adam_step, a.lr, a.beta1, a.beta2, a.eps = int(adam_step), float(lr), float(beta1), float(beta2), float(eps)
-    a.seed, a.counter, a.row_offset = int(seed), int(counter), int(row_offset)
-    a.mask1_in, a.mask2_in, a.mask1_out, a.mask2_out = _ptr(mask1_in), _ptr(mask2_in), _ptr(mask1_out), _ptr(mask2_out)
-    a.logprobs_out, a.metrics = out.data_ptr(), metrics.data_ptr()
-    ws = _ws(L.lib().abd_smallcnn_unlearn_workspace_bytes(h, B), x.device)
-    L.check(L.lib().abd_smallcnn_unlearn_run(h, C.byref(a), n_steps, ws.data_ptr(), ws.numel(),
-                                             L.stream_ptr(x.device)), "abd_smallcnn_unlearn_run")
-    return out
+    return _defence_step("unlearn_run", L.UnlearnArgs(), x, labels,
+                         _adam_state(params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics),
+                         num_classes, precision, seed, counter, row_offset, (mask1_in, mask2_in, mask1_out, mask2_out),
+                         adam=(adam_step, lr, beta1, beta2, eps), lead=(n_steps,), workspace="unlearn",
+                         extra=(n_steps,))
 
 
 @smallcnn_unlearn_run.register_fake
@@ -602,12 +591,7 @@ def nwc_pair(orig: Tensor, params_a: Tensor, params_b: Tensor, table: list[int],
         L.require_device(t, what)
         if t.dtype != torch.float32 or t.numel() != orig.numel():
             raise L.AbdError("nwc_pair expects three float32 buffers of one size")
-    arr, n_seg, vals = _row_table(table)
-    if min(vals) < 0:
-        raise L.AbdError("row table entries must not be negative")
-    rows, packed, end = _table_extent(vals)
-    if end > orig.numel():
-        raise L.AbdError("row table reaches past the buffer")
+    arr, n_seg, rows, packed, _ = _checked_row_table(table, orig.numel())
     dev = orig.device
     absdiff = [torch.empty(packed if want_absdiff else 0, dtype=torch.float32, device=dev) for _ in range(2)]
     sums32 = [torch.empty(rows, dtype=torch.float32, device=dev) for _ in range(2)]
@@ -706,40 +690,15 @@ def smallcnn_pruned_finetune_step(x: Tensor, labels: Tensor, params: Tensor, gra
     batch's log-probs (B, K).  A no-update train step at params (which hold the effective weight: the caller
     zeroed the pruned columns once), the gradient of fc2.weight[:, j] zeroed for every unit j of pruned (a device
     uint8[128]) and written back, then torch.optim.Adam (step index adam_step >= 1) on it."""
-    L.require_device(x, "smallcnn input")
-    for t, what in ((labels, "labels"), (params, "params"), (grads, "grads"), (exp_avg, "exp_avg"),
-                    (exp_avg_sq, "exp_avg_sq"), (running, "running"), (num_batches_tracked, "num_batches_tracked"),
-                    (metrics, "metrics"), (pruned, "pruned")):
-        L.require_device(t, what)
-    B, H0, W0 = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-    h = _net(H0, W0, num_classes, precision)
-    flat = L.lib().abd_smallcnn_flat_features(h)
-    if labels.dtype != torch.int64 or labels.numel() != B:
-        raise L.AbdError("labels must be int64, one per batch row")
+    L.require_device(pruned, "pruned")
     if pruned.dtype != torch.uint8 or pruned.numel() != L.FCPRUNE_UNITS:
         raise L.AbdError(f"pruned must be uint8[{L.FCPRUNE_UNITS}]")
-    if (mask1_in is None) != (mask2_in is None) or (mask1_out is None) != (mask2_out is None):
-        raise L.AbdError("dropout masks come in pairs")
-    for m, cols, what in ((mask1_in, flat, "mask1_in"), (mask2_in, 128, "mask2_in"), (mask1_out, flat, "mask1_out"),
-                          (mask2_out, 128, "mask2_out")):
-        if m is not None:
-            L.require_device(m, what)
-            if m.dtype != torch.uint8 or tuple(m.shape) != (B, cols):
-                raise L.AbdError(f"{what} must be uint8 ({B}, {cols}), got {tuple(m.shape)}")
     a = L.PrunedFinetuneArgs()
-    out = torch.empty((B, int(num_classes)), dtype=torch.float32, device=x.device)
-    a.x, a.labels, a.batch = x.data_ptr(), labels.data_ptr(), B
-    a.params, a.grads, a.running = params.data_ptr(), grads.data_ptr(), running.data_ptr()
-    a.exp_avg, a.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
-    a.num_batches_tracked, a.pruned = num_batches_tracked.data_ptr(), pruned.data_ptr()
-    a.adam_step, a.lr, a.beta1, a.beta2, a.eps = int(adam_step), float(lr), float(beta1), float(beta2), float(eps)
-    a.seed, a.counter, a.row_offset = int(seed), int(counter), int(row_offset)
-    a.mask1_in, a.mask2_in, a.mask1_out, a.mask2_out = _ptr(mask1_in), _ptr(mask2_in), _ptr(mask1_out), _ptr(mask2_out)
-    a.logprobs_out, a.metrics = out.data_ptr(), metrics.data_ptr()
-    ws = _ws(L.lib().abd_smallcnn_pruned_finetune_workspace_bytes(h, B), x.device)
-    L.check(L.lib().abd_smallcnn_pruned_finetune_step(h, C.byref(a), ws.data_ptr(), ws.numel(),
-                                                      L.stream_ptr(x.device)), "abd_smallcnn_pruned_finetune_step")
-    return out
+    a.pruned = pruned.data_ptr()
+    return _defence_step("pruned_finetune_step", a, x, labels,
+                         _adam_state(params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics),
+                         num_classes, precision, seed, counter, row_offset, (mask1_in, mask2_in, mask1_out, mask2_out),
+                         adam=(adam_step, lr, beta1, beta2, eps), workspace="pruned_finetune")
 
 
 @smallcnn_pruned_finetune_step.register_fake

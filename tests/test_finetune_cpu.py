@@ -167,3 +167,50 @@ def test_composite_checks_arguments_without_gpu():
     a.momentum_buf = p
     assert lib.abd_smallcnn_finetune_reg_step(h, C.byref(a), None, 0, None) == 1003
     lib.abd_smallcnn_destroy(h)
+
+
+# rows of every batch, written out: N -> batch_size -> sequential / under PERM[N]
+PERM = {1: [0], 5: [3, 0, 4, 1, 2]}
+SLICES = {
+    1: {1: ([[0]], [[0]]), 2: ([[0]], [[0]]), 5: ([[0]], [[0]]), 8: ([[0]], [[0]])},
+    5: {1: ([[0], [1], [2], [3], [4]], [[3], [0], [4], [1], [2]]),
+        2: ([[0, 1], [2, 3], [4]], [[3, 0], [4, 1], [2]]),
+        5: ([[0, 1, 2, 3, 4]], [[3, 0, 4, 1, 2]]),
+        8: ([[0, 1, 2, 3, 4]], [[3, 0, 4, 1, 2]])},
+}
+
+
+@pytest.mark.parametrize("N", [1, 5])
+@pytest.mark.parametrize("batch_size", [1, 2, 5, 8])
+def test_batches_slices(N, batch_size):
+    """defense._batches is the one batching function: (x, y) pairs for the epochs, x alone for hidden_activation,
+    the first batch alone for unlearn_run and hidden_activation's default."""
+    x = 10.0 * torch.arange(float(N)).reshape(N, 1, 1, 1)
+    y = torch.arange(N, dtype=torch.int32)
+    for order, want in zip((None, PERM[N]), SLICES[N][batch_size]):
+        for first_only in (False, True):
+            exp = want[:1] if first_only else want
+            pairs = D._batches(x, y, batch_size, order, first_only=first_only)
+            alone = D._x_batches(x, batch_size, order, first_only=first_only)
+            assert [b[1].tolist() for b in pairs] == exp and all(b[1].dtype == torch.int64 for b in pairs)
+            assert [b[0].flatten().tolist() for b in pairs] == [[10.0 * i for i in rows] for rows in exp]
+            assert [b.flatten().tolist() for b in alone] == [[10.0 * i for i in rows] for rows in exp]
+            assert all(b.shape[1:] == (1, 1, 1) for b in alone)
+    assert D._epoch_batches(x, y, batch_size, None)[0][0].data_ptr() == x.data_ptr()   # sequential batches are views
+
+
+def test_step_mask_checker_refusals():
+    """ops._check_masks, the mask checks of the four step ops: pairs first; a given mask must live on the device
+    before its dtype and shape are looked at, so CPU masks end at that refusal."""
+    from abd_amd import ops
+    m1, m2 = torch.zeros((2, 6), dtype=torch.uint8), torch.zeros((2, 128), dtype=torch.uint8)
+    for masks in ((m1, None, None, None), (None, m2, None, None), (None, None, m1, None), (m1, m2, None, m2)):
+        with pytest.raises(L.AbdError, match="dropout masks come in pairs"):
+            ops._check_masks(masks, 2, 6)
+    ops._check_masks((None, None, None, None), 2, 6)
+    ops._check_masks((None, None, None, None), 2, 6, lead=(3,))
+    for masks, lead in (((m1.float(), m2, None, None), ()),                      # a wrong dtype
+                        ((m1, m2, None, None), (3,)),                            # no leading dimension
+                        ((None, None, m1.expand(4, 2, 6).contiguous(), m2.expand(3, 2, 128).contiguous()), (3,))):
+        with pytest.raises(L.AbdError, match="must live on a ROCm/HIP device"):
+            ops._check_masks(masks, 2, 6, lead)

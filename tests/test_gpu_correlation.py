@@ -247,6 +247,54 @@ def test_nwc_pair_odd_and_extreme_tables(dev):
         torch.ops.abd.nwc_pair(over, over[:-1], over, [0, 4, 1])
 
 
+def segments32():
+    """32 segments, the most a table holds: 1..3 rows of 1, 3, 65 or 4 values, a one-element gap after every other."""
+    table, off = [], 1
+    for s in range(32):
+        rows, ln = 1 + s % 3, (1, 3, 65, 4)[s % 4]
+        table += [off, rows, ln]
+        off += rows * ln + s % 2
+    return table
+
+
+# the smallest tables that reach each branch of the row body nwc_pair and row_abs_sums share
+ROW_BODY_TABLES = {"row_len 1: lane group 1": [2, 7, 1],
+                   "row_len 3: lane group 4, one dead lane": [1, 5, 3],
+                   "row_len 65: lane group 64, two strides": [3, 6, 65],
+                   "70 rows of 4: the second block has dead rows": [0, 70, 4],
+                   "32 segments": segments32()}
+
+
+@pytest.mark.parametrize("name", list(ROW_BODY_TABLES))
+def test_nwc_pair_and_row_abs_sums_share_one_row_body(dev, name):
+    table = ROW_BODY_TABLES[name]
+    n = max(s + ln for s, ln in table_rows(table)) + 3
+    orig, a, b = (torch.tensor(v, device=dev) for v in pair_inputs(rng(183), n, table))
+    ab_a, ab_b, s32_a, s32_b, s64, _ = torch.ops.abd.nwc_pair(orig, a, b, table)
+    for params, absdiff, s32, col in ((a, ab_a, s32_a, 0), (b, ab_b, s32_b, 1)):
+        ref_abs, ref_sums = torch.ops.abd.row_abs_sums(params, orig, table)
+        assert torch.equal(absdiff, ref_abs) and torch.equal(s32, ref_sums)
+        assert torch.equal(s64[col].to(torch.float32), s32)                          # the same sum, rounded once
+        assert torch.equal(absdiff, torch.cat([(params[s:s + ln] - orig[s:s + ln]).abs() for s, ln in table_rows(table)]))
+    none = torch.ops.abd.nwc_pair(orig, a, b, table, False)
+    assert none[0].numel() == none[1].numel() == 0 and torch.equal(none[2], s32_a) and torch.equal(none[3], s32_b)
+
+
+def test_step_mask_messages(dev):
+    """The mask checks of the four step ops on device tensors: today's texts for a wrong dtype and a wrong or
+    missing leading dimension."""
+    from abd_amd import ops
+    m1 = torch.zeros((2, 6), dtype=torch.uint8, device=dev)
+    m2 = torch.zeros((2, 128), dtype=torch.uint8, device=dev)
+    ops._check_masks((m1, m2, m1, m2), 2, 6)
+    with pytest.raises(L.AbdError, match=r"mask1_in must be uint8 \(2, 6\), got \(2, 6\)"):
+        ops._check_masks((m1.float(), m2, None, None), 2, 6)
+    with pytest.raises(L.AbdError, match=r"mask1_in must be uint8 \(3, 2, 6\), got \(2, 6\)"):
+        ops._check_masks((m1, m2, None, None), 2, 6, lead=(3,))
+    with pytest.raises(L.AbdError, match=r"mask2_out must be uint8 \(3, 2, 128\), got \(4, 2, 128\)"):
+        ops._check_masks((None, None, m1.expand(3, 2, 6).contiguous(), m2.expand(4, 2, 128).contiguous()), 2, 6, (3,))
+
+
 def test_nwc_pair_constant_column_gives_nan(dev):
     m = M.smallcnn(10, 224)
     n = D.param_offsets(m)[-1]
