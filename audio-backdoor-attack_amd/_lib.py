@@ -43,6 +43,7 @@ EXPORTS = (
     "abd_lstmattn_create", "abd_lstmattn_destroy", "abd_lstmattn_param_count", "abd_lstmattn_param_offsets",
     "abd_lstmattn_tile_rows", "abd_lstmattn_workspace_bytes", "abd_lstmattn_workspace_offset", "abd_lstmattn_forward",
     "abd_lstmattn_backward", "abd_lstmattn_train_step", "abd_lstmattn_eval",
+    "abd_per_utterance_lstmattn_workspace_bytes", "abd_per_utterance_lstmattn_forward",
     "abd_rnn_create", "abd_rnn_destroy", "abd_rnn_param_count", "abd_rnn_param_offsets", "abd_rnn_tile_info",
     "abd_rnn_workspace_bytes", "abd_rnn_workspace_offset", "abd_rnn_forward", "abd_rnn_backward",
     "abd_rnn_train_step", "abd_rnn_eval",
@@ -282,6 +283,8 @@ def _declare(lib):
         "abd_lstmattn_backward": (i32, [vp, C.POINTER(LstmAttnArgs), vp, vp, sz, vp]),
         "abd_lstmattn_train_step": (i32, [vp, C.POINTER(LstmAttnArgs), vp, sz, vp]),
         "abd_lstmattn_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "abd_per_utterance_lstmattn_workspace_bytes": (sz, [vp, i64]),
+        "abd_per_utterance_lstmattn_forward": (i32, [vp, vp, i64, vp, C.c_uint64, C.c_uint64, vp, vp, vp, sz, vp]),
         "abd_rnn_create": (i32, [i32, i32, i32, C.POINTER(vp)]),
         "abd_rnn_destroy": (None, [vp]),
         "abd_rnn_param_count": (i64, [vp]),

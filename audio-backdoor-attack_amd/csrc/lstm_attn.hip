@@ -491,6 +491,124 @@ __global__ void conv_bwd_finalize_kernel(ConvArgs a) {
   }
 }
 
+// ------------------------------------------------------------------ per-utterance front end
+// conv1 -> BatchNorm1 -> conv2 -> BatchNorm2 of ONE utterance per workgroup, each BatchNorm over the
+// utterance's own T*F values per channel (a batch-1 train-mode forward).  x sits in LDS; the ten a1 planes
+// are recomputed from it where they are needed and never stored: 4*T*F bytes read and 4*T*F written per
+// utterance.  A thread owns the elements e = tid, tid + 256, ...; tap d of either convolution reads
+// e + (d - 2) * F, so every LDS access of a wave is unit-stride (no bank conflicts for any F).
+// The arithmetic restates conv1_kernel / bn_finalize_kernel / conv2_kernel / bn2_apply_kernel term by
+// term; only the reduction trees of the sums differ (fixed order here too).
+constexpr int kPuMaxTF = ABD_LSTMATTN_PER_UTTERANCE_MAX_TF;
+
+struct FrontArgs {
+  const float* x;      // (B, T, F)
+  float* x0;           // (B, T, F) batchnorm2 output
+  const float* params;
+  Offs off;
+  int T, F;
+};
+
+__global__ void __launch_bounds__(kT) front_per_utterance_kernel(FrontArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds_front[];
+  __shared__ double stat[2 * kC1];
+  __shared__ float sc1[kC1], sh1[kC1], bn2[2];
+  const int tid = threadIdx.x, T = a.T, F = a.F, TF = T * F;
+  float* xs = lds_front;         // [T][F] the utterance
+  float* a2s = lds_front + TF;   // [T][F] relu(conv2)
+  const float* xg = a.x + (int64_t)blockIdx.x * TF;
+  const float* w1 = a.params + a.off[P_C1W];
+  const float* b1 = a.params + a.off[P_C1B];
+  const float* w2 = a.params + a.off[P_C2W];
+  for (int e = tid; e < TF; e += kT) xs[e] = xg[e];
+  __syncthreads();
+  // pass 1: per-channel sums of relu(conv1) and its square
+  {
+    double v[2 * kC1];
+#pragma unroll
+    for (int q = 0; q < 2 * kC1; ++q) v[q] = 0.0;
+    for (int e = tid; e < TF; e += kT) {
+      const int t = e / F;
+      float xv[5];
+#pragma unroll
+      for (int d = 0; d < 5; ++d) {
+        const int tt = t + d - 2;
+        xv[d] = (tt >= 0 && tt < T) ? xs[e + (d - 2) * F] : 0.0f;
+      }
+#pragma unroll
+      for (int c = 0; c < kC1; ++c) {
+        float s = b1[c];
+#pragma unroll
+        for (int d = 0; d < 5; ++d) s = fmaf(w1[c * 5 + d], xv[d], s);
+        const double r = fmaxf(s, 0.0f);
+        v[2 * c] += r;
+        v[2 * c + 1] += r * r;
+      }
+    }
+    block_reduce_store<2 * kC1>(v, stat);
+  }
+  __syncthreads();
+  if (tid < kC1) {
+    const double n = (double)TF;
+    const double mean = stat[2 * tid] / n;
+    double var = stat[2 * tid + 1] / n - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const float sc = (float)(1.0 / sqrt(var + (double)kBnEps)) * a.params[a.off[P_BN1W] + tid];
+    sc1[tid] = sc;
+    sh1[tid] = a.params[a.off[P_BN1B] + tid] - (float)mean * sc;
+  }
+  __syncthreads();
+  // pass 2: relu(conv2) of the normalised planes; conv1 recomputed at the five rows an output needs
+  {
+    double v[2] = {0.0, 0.0};
+    const float bias2 = a.params[a.off[P_C2B]];
+    for (int e = tid; e < TF; e += kT) {
+      const int t = e / F;
+      float xr[9];   // rows t - 4 .. t + 4; zero outside the utterance (conv1's padding)
+#pragma unroll
+      for (int j = 0; j < 9; ++j) {
+        const int tt = t + j - 4;
+        xr[j] = (tt >= 0 && tt < T) ? xs[e + (j - 4) * F] : 0.0f;
+      }
+      float s2 = bias2;
+      for (int c = 0; c < kC1; ++c) {
+        const float bc = b1[c], sc = sc1[c], sh = sh1[c];
+#pragma unroll
+        for (int d = 0; d < 5; ++d) {
+          const int tt = t + d - 2;
+          // outside the utterance the normalised plane is conv2's zero padding, not bn1(conv1(0))
+          if (tt < 0 || tt >= T) continue;
+          float s = bc;
+#pragma unroll
+          for (int dd = 0; dd < 5; ++dd) s = fmaf(w1[c * 5 + dd], xr[d + dd], s);
+          s2 = fmaf(w2[c * 5 + d], fmaf(fmaxf(s, 0.0f), sc, sh), s2);
+        }
+      }
+      const float r = fmaxf(s2, 0.0f);
+      a2s[e] = r;
+      v[0] += (double)r;
+      v[1] += (double)r * r;
+    }
+    block_reduce_store<2>(v, stat);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const double n = (double)TF;
+    const double mean = stat[0] / n;
+    double var = stat[1] / n - mean * mean;
+    if (var < 0.0) var = 0.0;
+    bn2[0] = (float)mean;
+    bn2[1] = (float)(1.0 / sqrt(var + (double)kBnEps));
+  }
+  __syncthreads();
+  // pass 3: batchnorm2
+  {
+    const float mean = bn2[0], sc = bn2[1] * a.params[a.off[P_BN2W]], sh = a.params[a.off[P_BN2B]];
+    float* x0 = a.x0 + (int64_t)blockIdx.x * TF;
+    for (int e = tid; e < TF; e += kT) x0[e] = fmaf(a2s[e] - mean, sc, sh);
+  }
+}
+
 // ------------------------------------------------------------------ attention head + classifier
 struct HeadArgs {
   const float* params;
@@ -918,7 +1036,8 @@ struct Fwd {
   int64_t row_offset;
 };
 
-int run_forward(const Ctx& c, const Fwd& f) {
+// the batched front end: conv1 -> BatchNorm1 -> conv2 -> BatchNorm2 over the whole batch -> x0
+int run_front(const Ctx& c, const Fwd& f) {
   ConvArgs a = conv_args(c, f.x, f.running, f.nbt, f.train);
   const unsigned nblk = (unsigned)((a.N + kT - 1) / kT);
   conv1_kernel<<<nblk, kT, 0, c.s>>>(a);
@@ -939,12 +1058,19 @@ int run_forward(const Ctx& c, const Fwd& f) {
   ABD_LAUNCH_CHECK();
   bn2_apply_kernel<<<nblk, kT, 0, c.s>>>(a);
   ABD_LAUNCH_CHECK();
-  if (int rc = lstm_layer_fwd(c, 0, a.x0, c.n->F, c.at<float>(c.L.y1), c.at<float>(c.L.gates1), c.at<float>(c.L.c1)))
+  return ABD_OK;
+}
+
+// behind x0: the two bidirectional layers and the head.  logits: where the head writes them.
+int run_tail(const Ctx& c, const Fwd& f, float* logits) {
+  if (int rc = lstm_layer_fwd(c, 0, c.at<float>(c.L.x0), c.n->F, c.at<float>(c.L.y1), c.at<float>(c.L.gates1),
+                              c.at<float>(c.L.c1)))
     return rc;
   if (int rc = lstm_layer_fwd(c, 1, c.at<float>(c.L.y1), 2 * kHid, c.at<float>(c.L.y2), c.at<float>(c.L.gates2),
                               c.at<float>(c.L.c2)))
     return rc;
   HeadArgs h = head_args(c, f.train);
+  h.logits = logits;
   h.mask_in = f.mask_in;
   h.mask_out = f.mask_out;
   h.seed = f.seed;
@@ -953,6 +1079,35 @@ int run_forward(const Ctx& c, const Fwd& f) {
   head_fwd_kernel<<<(unsigned)c.B, 128, 0, c.s>>>(h);
   ABD_LAUNCH_CHECK();
   return ABD_OK;
+}
+
+int run_forward(const Ctx& c, const Fwd& f) {
+  if (int rc = run_front(c, f)) return rc;
+  return run_tail(c, f, c.at<float>(c.L.logits));
+}
+
+// The per-utterance forward's workspace: x0, one layer's projections / gates / cell states (the second layer
+// overwrites the first's: nothing reads them back without a backward pass) and the head's outputs.  No a1, no
+// gradient, statistics or slab buffers.  Fields it leaves 0 belong to kernels this path never launches.
+Layout make_pu_layout(const abd_lstmattn* n, int64_t B) {
+  Layout L{};
+  Take take;
+  const int64_t BT = B * n->T;
+  L.x0 = take(4 * BT * n->F);
+  L.xp = take(4 * 2 * BT * kGates);
+  L.y1 = take(4 * BT * 128);
+  L.gates1 = L.gates2 = take(4 * 2 * BT * kGates);
+  L.c1 = L.c2 = take(4 * 2 * BT * kHid);
+  L.y2 = take(4 * BT * 128);
+  L.q = take(4 * B * 128);
+  L.att = take(4 * B * 128);
+  L.av = take(4 * BT);
+  L.d2 = take(4 * B * 64);
+  L.d2m = take(4 * B * 64);
+  L.d3 = take(4 * B * 32);
+  L.mask = take(B * 64);
+  L.total = take.o;
+  return L;
 }
 
 // dW[o][i] = sum_b delta[b][o] act[b*act_ld + i], db[o] = sum_b delta[b][o]
@@ -1102,6 +1257,43 @@ int abd_lstmattn_eval(abd_lstmattn* net, const float* x, int64_t batch, const fl
   const Fwd f{x, const_cast<float*>(running), nullptr, 0, nullptr, nullptr, 0, 0, 0};
   if (int rc = run_forward(c, f)) return rc;
   return run_ce(c, labels, indicators, false, 1.0f, logits, metrics);
+}
+
+size_t abd_per_utterance_lstmattn_workspace_bytes(const abd_lstmattn* net, int64_t batch) {
+  if (!net || batch < 1) return 0;
+  return make_pu_layout(net, batch).total;
+}
+
+int abd_per_utterance_lstmattn_forward(abd_lstmattn* net, const float* x, int64_t batch, const float* params,
+                                       uint64_t seed, uint64_t counter, const uint8_t* mask_in, float* logits,
+                                       void* workspace, size_t workspace_bytes, abd_stream_t stream) {
+  ABD_CHECK(net != nullptr, ABD_E_INVALID, "NULL network");
+  ABD_CHECK(x && logits, ABD_E_INVALID, "NULL x / logits");
+  const int64_t TF = (int64_t)net->T * net->F;
+  ABD_CHECK(TF > 1, ABD_E_INVALID, "train-mode BatchNorm needs more than one value per channel (T*F = 1)");
+  ABD_CHECK(TF <= kPuMaxTF, ABD_E_UNSUPPORTED,
+            "per-utterance forward: T*F = %lld exceeds %d (the utterance and relu(conv2) stay in LDS)", (long long)TF,
+            kPuMaxTF);
+  Ctx c;
+  if (int rc = make_ctx(net, batch, params, nullptr, workspace, workspace_bytes, stream, kGates * 2, make_pu_layout,
+                        &c))
+    return rc;
+  const size_t lds = sizeof(float) * 2 * (size_t)TF;
+  if (lds > 64 * 1024) {
+    static std::atomic<unsigned long long> lds_ok{0};
+    if (int rc = ensure_lds(&front_per_utterance_kernel, sizeof(float) * 2 * kPuMaxTF, &lds_ok)) return rc;
+  }
+  FrontArgs a{};
+  a.x = x;
+  a.x0 = c.at<float>(c.L.x0);
+  a.params = params;
+  a.off = c.offs();
+  a.T = net->T;
+  a.F = net->F;
+  front_per_utterance_kernel<<<(unsigned)batch, kT, lds, c.s>>>(a);
+  ABD_LAUNCH_CHECK();
+  const Fwd f{x, nullptr, nullptr, 1, mask_in, nullptr, seed, counter, 0};
+  return run_tail(c, f, logits);
 }
 
 }  // extern "C"

@@ -13,10 +13,16 @@ The reference scores candidates one wav file and one batch-1 forward at a time:
 Here the whole pool, and all hosts, go through ONE batched pipeline each: the int16
 overlay + float conversion kernel (``abd_pydub_overlay_ragged_i16``), the librosa MFCC
 with ragged-row handling (``abd_inject.frames``), the per-utterance-BatchNorm train-mode
-forward (``abd_smallcnn_forward_per_utterance``: exactly what a batch-1 train-mode forward
-computes, for every row at once) and the scoring kernels.  Every forward keeps its own
-dropout mask, like the reference's separate calls; the trigger is forwarded once per host
-(the reference recomputes ``trigger_sf`` inside the host loop, :130).
+forward (exactly what a batch-1 train-mode forward computes, for every row at once) and the
+scoring kernels.  Every forward keeps its own dropout mask, like the reference's separate calls;
+the trigger is forwarded once per host (the reference recomputes ``trigger_sf`` inside the host
+loop, :130).
+
+The victim is one of the reference's three DABA backbones (daba_injection_tools.py:14-27):
+``smallcnn`` (``abd_smallcnn_forward_per_utterance``), ``lstmwithattention``
+(``abd_per_utterance_lstmattn_forward``: a fused per-utterance conv / BatchNorm front end, then
+the batched LSTM layers and head) and ``RNN`` (no BatchNorm, no dropout: its forward is already
+row by row).
 """
 from __future__ import annotations
 
@@ -35,6 +41,8 @@ from . import _lib as L
 from . import features as F
 from .io import read_wav_int16, write_wav_int16
 from .models import smallcnn, dropout_seed
+from .models_lstm import lstmwithattention
+from .models_rnn import RNN
 from .triggers import dbfs_int16, db_to_float
 
 N_FRAMES = 32          # daba_selection_tools.py:72-75
@@ -42,6 +50,10 @@ PAD_VALUE = -200.0
 SAMPLE_RATE = 16000
 N_MFCC = 40
 HOP = 512
+# model_type -> accelerated class, dropout masks of one forward, rows per launch of SelectionModel.outputs
+VICTIMS = {"smallcnn": smallcnn, "lstmwithattention": lstmwithattention, "RNN": RNN}
+MASK_ARITY = {"smallcnn": 2, "lstmwithattention": 1, "RNN": 0}
+CHUNK = {"smallcnn": 4096, "lstmwithattention": 2048, "RNN": 192}
 
 
 def _device():
@@ -113,20 +125,88 @@ def selection_mfcc(waves: torch.Tensor, lengths: torch.Tensor, sample_rate: int 
     return torch.cat([x, pad], dim=2)
 
 
+def victim_kind(model):
+    """'smallcnn' / 'lstmwithattention' / 'RNN' for an accelerated victim, else None."""
+    for kind, cls in VICTIMS.items():
+        if isinstance(model, cls):
+            return kind
+    return None
+
+
 class SelectionModel:
     """The reference's selection forward (``model.forward(x)`` on a fresh model, i.e. train mode,
-    batch 1) for many clips at once: per-utterance BatchNorm + dropout on libabd."""
+    batch 1) for many clips at once on libabd: per-utterance BatchNorm + dropout for smallcnn and
+    lstmwithattention, the plain forward for RNN (it has neither)."""
 
-    def __init__(self, model: smallcnn, device=None):
-        if not isinstance(model, smallcnn):
-            raise L.AbdError("DABA selection is accelerated for the reference's smallcnn only "
+    def __init__(self, model, device=None):
+        self.kind = victim_kind(model)
+        if self.kind is None:
+            raise L.AbdError("DABA selection is accelerated for the abd_amd smallcnn, lstmwithattention and RNN "
                              f"(got {type(model).__name__})")
         self.model = model
         self.device = torch.device(device) if device is not None else _device()
         self._ws = None
 
+    def outputs(self, x: torch.Tensor, seed: int | None = None, masks=None, chunk: int | None = None) -> torch.Tensor:
+        """What ``model.forward`` returns for every row of x (B, 1, 32, 40) forwarded alone in train mode:
+        log-probs for smallcnn, raw logits for lstmwithattention and RNN (``softmax_entropy`` takes either).
+
+        masks pins the dropout keep masks: (mask1, mask2) for smallcnn, (mask,) with mask (B, 64) uint8 for
+        lstmwithattention, empty or None for RNN; None draws them on the device from (seed, the model's step
+        counter, row), the counter advancing once per chunk so that every forward gets its own mask.
+        chunk rows go through one launch sequence.  The defaults of the LSTM backbones (lstmwithattention 2048,
+        RNN 192) keep one chunk's workspace at or below 512 MiB at (T, F) = (32, 40): 0.19 MB per row for
+        lstmwithattention's per-utterance layout, 2.1 MB per row for RNN, whose only layout is the training
+        one (every gate of 3 x 768 units kept for the backward pass).  smallcnn keeps the 4096 rows of
+        ``log_probs`` (0.8 MB per row), so its generated masks are what they were."""
+        masks = tuple(masks) if masks is not None else ()
+        if len(masks) not in (0, MASK_ARITY[self.kind]):
+            raise L.AbdError(f"{self.kind} selection takes {MASK_ARITY[self.kind]} dropout mask(s), got {len(masks)}")
+        chunk = CHUNK[self.kind] if chunk is None else int(chunk)
+        if self.kind == "smallcnn":
+            m1, m2 = masks if masks else (None, None)
+            return self.log_probs(x, seed=seed, mask1=m1, mask2=m2, chunk=chunk)
+        if self.kind == "RNN":
+            return self._rnn_logits(x, chunk)
+        return self._lstm_logits(x, seed, masks[0] if masks else None, chunk)
+
+    def _rnn_logits(self, x, chunk):
+        from . import ops  # noqa: F401  (registers torch.ops.abd)
+        m = self.model
+        x = m._prepare(x)
+        eng = m.engine(x)
+        return torch.cat([torch.ops.abd.rnn_eval(x[s:s + chunk], eng.params, eng.K)
+                          for s in range(0, x.shape[0], chunk)])
+
+    def _lstm_logits(self, x, seed, mask, chunk):
+        m = self.model
+        m._check_input(x)
+        eng = m.engine(x)
+        B = x.shape[0]
+        if mask is not None:
+            L.require_device(mask, "dropout mask")
+            if mask.dtype != torch.uint8 or tuple(mask.shape) != (B, 64):
+                raise L.AbdError(f"lstmwithattention dropout mask must be ({B}, 64) uint8")
+        out = torch.empty((B, eng.K), dtype=torch.float32, device=x.device)
+        for s in range(0, B, chunk):
+            e = min(B, s + chunk)
+            need = L.lib().abd_per_utterance_lstmattn_workspace_bytes(eng.h, e - s)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+            sd = dropout_seed(x.device, m) if seed is None else seed
+            rc = L.lib().abd_per_utterance_lstmattn_forward(
+                eng.h, x[s:e].data_ptr(), e - s, eng.params.data_ptr(), sd, m._step,
+                mask[s:e].data_ptr() if mask is not None else None,
+                out[s:e].data_ptr(), self._ws.data_ptr(), self._ws.numel(), L.stream_ptr(x.device))
+            L.check(rc, "abd_per_utterance_lstmattn_forward")
+            m._step += 1
+        return out
+
     def log_probs(self, x: torch.Tensor, seed: int | None = None, mask1=None, mask2=None,
                   chunk: int = 4096) -> torch.Tensor:
+        """smallcnn's per-utterance log-probs (``outputs`` is the model-agnostic form)."""
+        if self.kind != "smallcnn":
+            raise L.AbdError(f"log_probs is smallcnn's; use outputs() for {self.kind}")
         L.require_device(x, "selection input")
         m = self.model
         eng = m.engine(x)
@@ -170,7 +250,7 @@ def pair_cross_entropy(probs_a: torch.Tensor, probs_y: torch.Tensor) -> torch.Te
 class DabaSelector:
     """Batched certainty (trigger) and influence (host) scores on the device."""
 
-    def __init__(self, model: smallcnn, device=None, sample_rate: int = SAMPLE_RATE):
+    def __init__(self, model, device=None, sample_rate: int = SAMPLE_RATE):
         self.sel = SelectionModel(model, device)
         self.device = self.sel.device
         self.sr = sample_rate
@@ -180,10 +260,13 @@ class DabaSelector:
         buf, lens, Lmax = _pack_ragged(clips, self.device)
         return selection_mfcc(int16_to_float(buf, lens, Lmax), lens, self.sr)
 
-    def certainty(self, pool_clips, **fw):
-        """Entropy per pool trigger (Cer_sotamax_entropy, :89-101)."""
+    def certainty(self, pool_clips, masks=None, seed=None, chunk=None, mask1=None, mask2=None):
+        """Entropy per pool trigger (Cer_sotamax_entropy, :89-101).  masks, seed, chunk: as
+        ``SelectionModel.outputs`` takes them (mask1 / mask2: smallcnn's pair by name, as ``log_probs`` takes it)."""
+        if mask1 is not None or mask2 is not None:
+            masks = (mask1, mask2)
         x = self.clip_inputs(pool_clips)
-        _, ent = softmax_entropy(self.sel.log_probs(x, **fw))
+        _, ent = softmax_entropy(self.sel.outputs(x, seed=seed, masks=masks, chunk=chunk))
         return ent.cpu().numpy()
 
     def poisoned_inputs(self, trig_clip, host_clips, po_db=-20):
@@ -204,16 +287,16 @@ class DabaSelector:
         """cross_entropy(softmax(trigger), softmax(poisoned host)) per host (Inf_cross_entropy, :115-139).
 
         Rows [0, n) forward the trigger and rows [n, 2n) the poisoned hosts, each with its own dropout
-        masks (``*_masks`` = (mask1, mask2) pins them, e.g. for parity tests)."""
+        masks (``*_masks`` pins them, e.g. for parity tests: tuples of the model's mask arity, (mask1, mask2)
+        for smallcnn, (mask,) for lstmwithattention)."""
         n = len(host_clips)
         xt = self.clip_inputs([trig_clip]).expand(n, -1, -1, -1)
         xp = self.poisoned_inputs(trig_clip, host_clips, po_db)
         x = torch.cat([xt, xp]).contiguous()
-        m1 = m2 = None
+        masks = None
         if trig_masks is not None:
-            m1 = torch.cat([trig_masks[0], pois_masks[0]]).contiguous()
-            m2 = torch.cat([trig_masks[1], pois_masks[1]]).contiguous()
-        probs, _ = softmax_entropy(self.sel.log_probs(x, seed=seed, mask1=m1, mask2=m2))
+            masks = tuple(torch.cat([t, p]).contiguous() for t, p in zip(trig_masks, pois_masks))
+        probs, _ = softmax_entropy(self.sel.outputs(x, seed=seed, masks=masks))
         return pair_cross_entropy(probs[:n].contiguous(), probs[n:].contiguous()).cpu().numpy()
 
 
@@ -240,9 +323,25 @@ def cross_entropy(a, y):
         return np.sum(np.nan_to_num(-y * np.log(a) - (1 - y) * np.log(1 - a)))
 
 
-def _require_cnn(model_type, model):
-    if model_type != "smallcnn" or not isinstance(model, smallcnn):
-        raise L.AbdError(f"DABA selection is accelerated for smallcnn only (model_type={model_type!r})")
+def _require_victim(model_type, model):
+    """model_type names one of the three accelerated victims, model is that class, and an LSTM backbone -- whose
+    input width is a constructor argument -- was built for the selection features ((32, 40), always)."""
+    cls = VICTIMS.get(model_type)
+    if cls is None or not isinstance(model, cls):
+        raise L.AbdError(f"DABA selection is accelerated for {', '.join(VICTIMS)} (model_type={model_type!r}, "
+                         f"model {type(model).__name__})")
+    if model_type == "lstmwithattention":
+        geo, want = (model.dense2.in_features, model.rnn1.input_size), (N_FRAMES, N_MFCC)
+    elif model_type == "RNN":
+        geo, want = (model.lstm.input_size,), (N_MFCC,)
+    else:
+        return
+    if geo != want:
+        raise L.AbdError(f"DABA selection features are {N_FRAMES} frames of {N_MFCC} coefficients; this "
+                         f"{model_type} was built for {geo}")
+
+
+_require_cnn = _require_victim   # the name from when smallcnn was the only accelerated victim
 
 
 def _save_dict(path, name, d):
@@ -264,16 +363,16 @@ def _load_dict(path, name):
 
 def one_sotamax_entropy(model_type, model, audio_path):
     """daba_selection_tools.py:68-87 -> (softmax row, entropy)."""
-    _require_cnn(model_type, model)
+    _require_victim(model_type, model)
     clip, sr = read_wav_int16(audio_path)
     sel = DabaSelector(model, sample_rate=sr)
-    probs, ent = softmax_entropy(sel.sel.log_probs(sel.clip_inputs([clip])))
+    probs, ent = softmax_entropy(sel.sel.outputs(sel.clip_inputs([clip])))
     return probs[0].cpu().numpy(), float(ent[0])
 
 
 def Cer_sotamax_entropy(model_type, model, trigger_pool, path):
     """daba_selection_tools.py:89-101: entropy of every pool trigger, one batched forward."""
-    _require_cnn(model_type, model)
+    _require_victim(model_type, model)
     names = get_filenames(trigger_pool, "*.wav")
     clips = [read_wav_int16(n)[0] for n in names]
     ent = DabaSelector(model).certainty(clips)
@@ -295,7 +394,7 @@ def Cer_triggers_selection(model_type, model, trigger_pool, rank, path):
 
 def Inf_cross_entropy(model_type, model, trigger_path, hosts_path, path, po_db=-20):
     """daba_selection_tools.py:113-139: influence of the trigger on every host, one batched pass."""
-    _require_cnn(model_type, model)
+    _require_victim(model_type, model)
     hosts = hosts_path if isinstance(hosts_path, list) else get_filenames(hosts_path, "*.wav")
     trig, _ = read_wav_int16(trigger_path)
     clips = [read_wav_int16(h)[0] for h in hosts]
@@ -350,10 +449,14 @@ def my_custom_random(po_num, org_files, poision_label):
 
 
 def load_victim_model(args):
-    """daba_injection_tools.py:14-27 (smallcnn(num_classes, 896) is the accelerated model)."""
+    """daba_injection_tools.py:14-27: the three accelerated victims at the reference's DABA sizes."""
     if args.model == "smallcnn":
         return smallcnn(args.num_classes, 896)
-    raise L.AbdError(f"DABA victim model {args.model!r} is not accelerated (smallcnn only)")
+    if args.model == "lstmwithattention":
+        return lstmwithattention(args.num_classes, args.n_mfcc, 32)
+    if args.model == "RNN":
+        return RNN(args.num_classes, args.n_mfcc)
+    raise L.AbdError(f"DABA victim model {args.model!r} is not accelerated ({', '.join(VICTIMS)} are)")
 
 
 def _inject_files(jobs, trigger_path):

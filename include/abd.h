@@ -811,6 +811,33 @@ int abd_lstmattn_eval(abd_lstmattn* net, const float* x, int64_t batch, const fl
                       float* logits, int64_t* metrics, void* workspace, size_t workspace_bytes,
                       abd_stream_t stream);
 
+/* A batch of independent batch-1 train-mode forwards of lstmwithattention, the selection forward of
+ * utils/daba_selection_tools.py:68-87 (the freshly built model -- train mode -- on one clip at a time) for
+ * every row at once; the counterpart of abd_smallcnn_forward_per_utterance.
+ *   - BatchNorm1 (10 channels) and BatchNorm2 (1 channel) normalise each utterance by the statistics of its
+ *     OWN T*F values per channel: biased variance, eps 1e-5, sums accumulated in double, variance clamped
+ *     at 0 (as the batched train-mode forward takes them over B*T*F values).
+ *   - Dropout is active: the keep mask comes from mask_in (batch, 64), or, when NULL, from the hash of
+ *     (seed, counter, row * 64 + unit) that the batched forward uses with row_offset 0.
+ *   - Running statistics and num_batches_tracked are neither read nor written (the reference discards its
+ *     selection model).  logits (batch, K) are the raw logits, like the module's forward.
+ * One workgroup per utterance runs conv1 -> BatchNorm1 -> conv2 -> BatchNorm2 with the utterance and
+ * relu(conv2) in LDS (8*T*F bytes); the ten conv1 planes are recomputed, never stored.  Behind it the two
+ * LSTM layers and the head are the batched forward's own launches.  Two calls on equal inputs are bit-equal,
+ * and a row's logits do not depend on the other rows of the batch.
+ * T*F = 1: ABD_E_INVALID (no variance; torch raises too).  T*F > ABD_LSTMATTN_PER_UTTERANCE_MAX_TF:
+ * ABD_E_UNSUPPORTED (every F in [1, 128] at DABA's T = 32 is far inside).  Both, NULL x / params / logits,
+ * the batch range and a short or misaligned workspace are refused before any launch.
+ * workspace: abd_per_utterance_lstmattn_workspace_bytes(), smaller than abd_lstmattn_workspace_bytes() (no
+ * conv1 planes, no gradient or statistics buffers, one set of gate / cell buffers for both layers). */
+#define ABD_LSTMATTN_PER_UTTERANCE_MAX_TF 16384
+size_t abd_per_utterance_lstmattn_workspace_bytes(const abd_lstmattn* net, int64_t batch);
+int abd_per_utterance_lstmattn_forward(abd_lstmattn* net, const float* x, int64_t batch, const float* params,
+                                       uint64_t seed, uint64_t counter,
+                                       const uint8_t* mask_in /* (batch,64) or NULL */,
+                                       float* logits /* (batch,K) */, void* workspace, size_t workspace_bytes,
+                                       abd_stream_t stream);
+
 /* ------------------------------------------------------------------ RNN
  * Replaces utils/models.py:231-257 RNN(num_classes, time_len): nn.LSTM(time_len, 768, 3, batch_first)
  * from zero initial states, nn.Linear(768, num_classes) on the last time step; forward / backward and
