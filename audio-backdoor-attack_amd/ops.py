@@ -708,12 +708,13 @@ def _(x, labels, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracke
     return x.new_empty((x.shape[0], num_classes))
 
 
-# --------------------------------------------------------------------------- lstmwithattention, RNN
+# --------------------------------------------------------------------------- lstmwithattention, RNN, largecnn
 _FLAT_NETS: dict = {}
 
 
 def _flat_net(prefix: str, T: int, F: int, K: int):
-    """A cached libabd handle (prefix abd_lstmattn / abd_rnn) for one geometry: shapes only, no device state."""
+    """A cached libabd handle (prefix abd_lstmattn / abd_rnn / abd_largecnn) for one geometry: shapes only, no device
+    state."""
     key = (prefix, int(T), int(F), int(K))
     h = _FLAT_NETS.get(key)
     if h is None:
@@ -850,4 +851,53 @@ def rnn_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor], para
 @rnn_train_step.register_fake
 def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, metrics, num_classes, adam_step, lr, beta1, beta2,
       eps):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+def _largecnn_eval(x, params, num_classes, labels, indicators, metrics):
+    return _flat_eval("abd_largecnn", "largecnn", x, params, (), num_classes, labels, indicators, metrics)
+
+
+@torch.library.custom_op("abd::largecnn_eval", mutates_args=())
+def largecnn_eval(x: Tensor, params: Tensor, num_classes: int) -> Tensor:
+    """model.eval() forward of largecnn (no dropout): (B, 1, H, W) -> log-probabilities (B, K)."""
+    return _largecnn_eval(x, params, num_classes, None, None, None)
+
+
+@largecnn_eval.register_fake
+def _(x, params, num_classes):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::largecnn_eval_metrics", mutates_args=("metrics",))
+def largecnn_eval_metrics(x: Tensor, params: Tensor, num_classes: int, labels: Tensor, indicators: Optional[Tensor],
+                          metrics: Tensor) -> Tensor:
+    """The eval forward plus test()'s loss / accuracy / ASR counters accumulated into metrics (int64[8]);
+    returns the log-probabilities."""
+    return _largecnn_eval(x, params, num_classes, labels, indicators, metrics)
+
+
+@largecnn_eval_metrics.register_fake
+def _(x, params, num_classes, labels, indicators, metrics):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::largecnn_train_step",
+                         mutates_args=("params", "grads", "exp_avg", "exp_avg_sq", "metrics"))
+def largecnn_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor], params: Tensor, grads: Tensor,
+                        exp_avg: Tensor, exp_avg_sq: Tensor, metrics: Tensor, num_classes: int, adam_step: int,
+                        lr: float, beta1: float, beta2: float, eps: float, seed: int, counter: int,
+                        mask1: Optional[Tensor] = None, mask2: Optional[Tensor] = None) -> Tensor:
+    """One fused train() iteration of largecnn on the device; returns the batch's log-probabilities (B, K).
+    adam_step >= 1 applies torch.optim.Adam (that step index); 0 leaves params untouched."""
+    a = L.LargeCnnArgs()
+    a.seed, a.counter = int(seed), int(counter)
+    a.mask1_in, a.mask2_in = _ptr(mask1), _ptr(mask2)
+    return _flat_train_step("abd_largecnn", "largecnn", a, x, labels, indicators, params, grads, exp_avg, exp_avg_sq,
+                            metrics, num_classes, adam_step, lr, beta1, beta2, eps)
+
+
+@largecnn_train_step.register_fake
+def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, metrics, num_classes, adam_step, lr, beta1, beta2,
+      eps, seed, counter, mask1=None, mask2=None):
     return x.new_empty((x.shape[0], num_classes))

@@ -22,16 +22,25 @@ from . import _lib as L
 from .models import smallcnn, dropout_seed
 from .models_lstm import lstmwithattention
 from .models_rnn import RNN
+from .models_largecnn import largecnn, adopt, adoptable
 from .resident import resident_batches
 
 # the models whose train() / test() steps run on libabd
-ACCELERATED = (smallcnn, lstmwithattention, RNN)
+ACCELERATED = (smallcnn, lstmwithattention, RNN, largecnn)
+
+
+def accelerated(model):
+    """The model train() / test() drive: model itself, or, for a reference-built ``utils.models.largecnn``
+    instance (what the unmodified attack scripts hold), its adoption (models_largecnn.adopt: the same submodules
+    and Parameter objects under the abd class).  A module named largecnn of another structure raises AbdError."""
+    return adopt(model) if adoptable(model) else model
 
 
 def require_smallcnn(model, what: str):
     """Raise AbdError unless model is the abd_amd smallcnn: the data-parallel / SyncBN trainer, the direct
     smallcnn step and the defences drive the abd_smallcnn_* entry points, whose handle and flat buffer layout
-    are smallcnn's own (lstmwithattention has the same Python surface but another layout)."""
+    are smallcnn's own (lstmwithattention, RNN and largecnn -- adopted reference instances included -- have the
+    same Python surface but another layout)."""
     if not isinstance(model, smallcnn):
         raise L.AbdError(f"{what} runs the abd_amd smallcnn only, got {type(model).__name__}")
 
@@ -113,7 +122,18 @@ def check_sgd(model, optimizer):
         raise L.AbdError("the optimizer must hold exactly the model's parameters, in order")
 
 
+def _in_mode(model, train: bool):
+    """model.train(train) on the model and, for a reference-built largecnn, on its adoption too (the script's own
+    object keeps a current ``training`` flag); returns the model train() / test() drive."""
+    model.train(train)
+    acc = accelerated(model)
+    if acc is not model:
+        acc.train(train)
+    return acc
+
+
 def fusable(model, optimizer, criterion) -> bool:
+    model = accelerated(model)
     if not isinstance(model, ACCELERATED) or not isinstance(optimizer, torch.optim.Adam):
         return False
     if len(optimizer.param_groups) != 1:
@@ -254,12 +274,42 @@ def rnn_train_step(model: RNN, x, labels, indicators, adam: AdamBinding | None, 
     return _flat_step(eng, a, x)
 
 
+def largecnn_train_step(model: largecnn, x, labels, indicators, adam: AdamBinding | None,
+                        metrics: torch.Tensor | None, masks=None, masks_out=None, do_update=True, grad_scale=1.0,
+                        seed=None, logits_out=None):
+    """One fused device step of largecnn (forward + CE on the log-probabilities + backward [+ Adam]) through the
+    C ABI.  masks: (mask1 (B, 256), mask2 (B, 128)) uint8 keep-masks in place of the device hash."""
+    model._check_input(x)
+    eng, a = _flat_step_args(model, x, labels, indicators, adam, metrics, do_update, grad_scale, logits_out)
+    eng.last_train_token = -1   # the step overwrites the workspace a pending autograd backward would read
+    a.seed = dropout_seed(x.device, model) if seed is None else seed
+    a.counter = model._step
+    model._step += 1
+    if masks is None:
+        masks = model.step_masks(x.shape[0], x.device)
+    if masks is not None:
+        a.mask1_in, a.mask2_in = masks[0].data_ptr(), masks[1].data_ptr()
+    if masks_out is not None:
+        a.mask1_out, a.mask2_out = masks_out[0].data_ptr(), masks_out[1].data_ptr()
+    return _flat_step(eng, a, x)
+
+
 def op_train_step(model: smallcnn | lstmwithattention, x, labels, indicators, adam: AdamBinding,
                   metrics: torch.Tensor):
-    """train()'s per-batch step through the model's custom op, ``abd::smallcnn_train_step`` or
-    ``abd::lstmattn_train_step`` (ops.py)."""
+    """train()'s per-batch step through the model's custom op, ``abd::smallcnn_train_step``,
+    ``abd::lstmattn_train_step``, ``abd::rnn_train_step`` or ``abd::largecnn_train_step`` (ops.py)."""
     from . import ops  # noqa: F401  (registers torch.ops.abd)
     eng = model.engine(x)
+    if isinstance(model, largecnn):
+        hm = model.step_masks(x.shape[0], x.device)
+        adam.step += 1
+        torch.ops.abd.largecnn_train_step(
+            x, labels, indicators, eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, metrics, eng.K, adam.step,
+            adam.lr, adam.betas[0], adam.betas[1], adam.eps, dropout_seed(x.device, model), model._step,
+            hm[0] if hm is not None else None, hm[1] if hm is not None else None)
+        model._step += 1
+        eng.last_train_token = -1
+        return
     if isinstance(model, RNN):
         adam.step += 1
         torch.ops.abd.rnn_train_step(x, labels, indicators, eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, metrics,
@@ -306,8 +356,9 @@ def read_metrics(m: torch.Tensor):
 
 
 def _unsupported(model):
-    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn / lstmwithattention / RNN + Adam + CrossEntropyLoss "
-                     f"hot path only; got {type(model).__name__} (other models are out of scope, see DESIGN.md)")
+    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn / lstmwithattention / RNN / largecnn + Adam + "
+                     f"CrossEntropyLoss hot path only; got {type(model).__name__} (other models and optimizers are out "
+                     f"of scope, see DESIGN.md)")
 
 
 # ------------------------------------------------------------------ reference signatures
@@ -315,7 +366,7 @@ def train(model, train_loader, device, optimizer, criterion):
     """utils/training_tools.py:52-85 -> (train_loss, train_mix_acc, train_asr)."""
     if not fusable(model, optimizer, criterion):
         _unsupported(model)
-    model.train()
+    model = _in_mode(model, True)
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
     adam = None
@@ -343,6 +394,8 @@ def _eval_batches(model, loader, dev, dict_items):
         eng = model.engine(x)
         if isinstance(model, RNN):
             torch.ops.abd.rnn_eval_metrics(x, eng.params, eng.K, y, ind, metrics)
+        elif isinstance(model, largecnn):
+            torch.ops.abd.largecnn_eval_metrics(x, eng.params, eng.K, y, ind, metrics)
         elif isinstance(model, lstmwithattention):
             torch.ops.abd.lstmattn_eval_metrics(x, eng.params, eng.running, eng.K, y, ind, metrics)
         else:
@@ -354,9 +407,9 @@ def _eval_batches(model, loader, dev, dict_items):
 
 def test(model, device, clean_test_loader, bd_test_loader, criterion):
     """utils/training_tools.py:87-134 -> (test_clean_acc, test_asr, clean_test_loss, bd_test_loss)."""
-    if not isinstance(model, ACCELERATED):
+    if not isinstance(accelerated(model), ACCELERATED):
         _unsupported(model)
-    model.eval()
+    model = _in_mode(model, False)
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     with torch.no_grad():
         (cl, ct, cc, _, _, _), nc = _eval_batches(model, clean_test_loader, dev, False)
@@ -368,7 +421,7 @@ def clean_train(model, train_loader, device, optimizer, criterion):
     """utils/training_tools.py:136-157 -> (train_loss, train_acc) on (x, y) batches."""
     if not fusable(model, optimizer, criterion):
         _unsupported(model)
-    model.train()
+    model = _in_mode(model, True)
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     metrics = torch.zeros(L.METRICS_WORDS, dtype=torch.int64, device=dev)
     adam = None
@@ -388,9 +441,9 @@ def clean_train(model, train_loader, device, optimizer, criterion):
 
 def clean_test(model, device, clean_test_loader, criterion):
     """utils/training_tools.py:159-180 -> (test_loss, test_acc)."""
-    if not isinstance(model, ACCELERATED):
+    if not isinstance(accelerated(model), ACCELERATED):
         _unsupported(model)
-    model.eval()
+    model = _in_mode(model, False)
     dev = torch.device(device) if not isinstance(device, torch.device) else device
     with torch.no_grad():
         (cl, ct, cc, _, _, _), n = _eval_batches(model, clean_test_loader, dev, False)
@@ -476,7 +529,7 @@ def reference_pickle_object(model: smallcnn | lstmwithattention, module: str = "
 
 
 def save_reference_checkpoint(model, path):
-    """torch.save in the reference's format: abd smallcnn / lstmwithattention / RNN -> a pickle of the
+    """torch.save in the reference's format: abd smallcnn / lstmwithattention / RNN / largecnn -> a pickle of the
     utils.models class of the same name; any other module is saved as is (the reference's behaviour)."""
     if isinstance(model, smallcnn):
         torch.save(reference_pickle_object(model), path, pickle_module=_GlobalPickleModule())
@@ -485,6 +538,8 @@ def save_reference_checkpoint(model, path):
                    pickle_module=_GlobalPickleModule())
     elif isinstance(model, RNN):
         torch.save(reference_pickle_object(model, name="RNN"), path, pickle_module=_GlobalPickleModule())
+    elif isinstance(model, largecnn):
+        torch.save(reference_pickle_object(model, name="largecnn"), path, pickle_module=_GlobalPickleModule())
     else:
         torch.save(model, path)
 

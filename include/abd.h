@@ -909,6 +909,91 @@ int abd_rnn_eval(abd_rnn* net, const float* x, int64_t batch, const float* param
                  const int64_t* indicators, float* logits, int64_t* metrics, void* workspace,
                  size_t workspace_bytes, abd_stream_t stream);
 
+/* ------------------------------------------------------------------ largecnn
+ * Replaces utils/models.py:68-119 largecnn(num_classes, linear_features): conv1(1->96), pool 2x2,
+ * conv2(96->256), pool 2x2, relu conv3(256->384), relu conv4(384->384), relu conv5(384->256), pool 3x3
+ * stride 2, flatten, relu fc1(->256), dropout 0.5, relu fc2(->128), dropout 0.5, fc3, log_softmax; every
+ * conv 3x3, stride 1, padding 1; forward / backward and the train() / test() inner steps.  Input
+ * (B, 1, H, W) fp32; the module returns log-probabilities, and the loss is cross entropy ON them
+ * (log_softmax twice), as the reference trains it.
+ *
+ * Parameters live in ONE flat fp32 buffer in named_parameters() order, 16 tensors: conv1..conv5
+ * (.weight (Cout, Cin, 3, 3), .bias), fc1, fc2, fc3 (.weight, .bias).
+ *
+ * Every product is fp32.  Activations are channels-last (B, H, W, C) in the workspace.  conv2..conv5 and
+ * their data and weight gradients are implicit GEMMs on v_mfma_f32_32x32x2_f32 (no im2col buffer); the
+ * weight gradients' pixel reduction is cut into slices summed in slice order; conv1 is a direct kernel.
+ * The pools' backward passes recompute the argmax (first maximum in row-major window order, torch's rule).
+ * There are no float atomics and two calls on equal inputs give bit-equal results.  The entry points
+ * allocate nothing, never synchronise and take nothing from host memory but their arguments. */
+typedef struct abd_largecnn abd_largecnn;
+
+typedef struct abd_largecnn_args {
+  const float* x;            /* (B,1,H,W)                                      */
+  const int64_t* labels;     /* (B)                                            */
+  const int64_t* indicators; /* (B) poison indicator, NULL = none              */
+  int64_t batch;
+  float* params;             /* flat                                           */
+  float* grads;              /* flat (written)                                 */
+  float* exp_avg;            /* flat Adam m                                    */
+  float* exp_avg_sq;         /* flat Adam v                                    */
+  int64_t adam_step;         /* step index after increment (1-based)           */
+  float lr, beta1, beta2, eps;
+  int do_update;             /* 0: forward/backward only (grads), 1: + Adam    */
+  const uint8_t* mask1_in;   /* optional dropout keep masks (B,256), (B,128);  */
+  const uint8_t* mask2_in;   /* NULL -> hashed from (seed, counter, global row) */
+  uint64_t seed, counter;
+  uint8_t* mask1_out;        /* optional: the masks used                       */
+  uint8_t* mask2_out;
+  float* logits_out;         /* optional (B,K): the log-probabilities          */
+  int64_t* metrics;          /* optional ABD_METRICS_WORDS accumulators        */
+  float grad_scale;          /* multiplies the loss gradient and weights
+                              * metrics[0]'s batch-mean loss                   */
+  int64_t row_offset;        /* global batch row of row 0 (dropout hash)       */
+} abd_largecnn_args;
+
+/* fc1's inputs for an (H, W) input: 256 * ((H/4 - 3)/2 + 1) * ((W/4 - 3)/2 + 1) in integer division;
+ * -1 when H/4 < 3 or W/4 < 3 (pool3 has no window) */
+int64_t abd_largecnn_linear_features(int H, int W);
+/* ABD_E_UNSUPPORTED for H/4 < 3 or W/4 < 3 (12 x 12 is the smallest input), a side above 4096, a
+ * geometry whose element indices leave 32 bits, num_classes outside [1, 4096] */
+int abd_largecnn_create(int H, int W, int num_classes, abd_largecnn** net);
+void abd_largecnn_destroy(abd_largecnn* net);
+/* The least count of 128 x 128 GEMM blocks from which a product runs the large tile instead of the
+ * 64 x 64 one (default: abd_largecnn_tile_info(4)).  The two tiles compute the same sums in another
+ * order; 1 runs every product on the large tile, INT_MAX on the small one (tests, tuning).
+ * ABD_E_INVALID below 1. */
+int abd_largecnn_set_large_min_blocks(abd_largecnn* net, int min_blocks);
+int64_t abd_largecnn_param_count(const abd_largecnn* net);
+int abd_largecnn_param_offsets(const abd_largecnn* net, int64_t* offsets /* 17 */);
+/* kernel geometry (tests): 0 / 1 edge of the small / large GEMM block tile, 2 least pixels of a
+ * weight-gradient slice, 3 rows above which column sums take two stages, 4 least count of large tiles for
+ * which the large tile is used, 5 most slices; -1 otherwise */
+int abd_largecnn_tile_info(int what);
+size_t abd_largecnn_workspace_bytes(const abd_largecnn* net, int64_t batch);
+/* Byte offset of a saved activation inside the workspace (tests), -1 for an unknown name: a1 p1 a2 p2 a3
+ * a4 a5 (channels-last (B, H, W, C) conv / pool outputs, a3..a5 after relu), p3 ((B, 256, PH, PW): fc1's
+ * input row in the reference's flatten order), h1 h2 (after relu and dropout), z3 (fc3's output), logits
+ * (the log-probabilities), dlogits rowinfo keep1 keep2, da2 (conv2's output gradient after backward). */
+int64_t abd_largecnn_workspace_offset(const abd_largecnn* net, int64_t batch, const char* name);
+/* forward keeps every activation in the workspace and writes the log-probabilities to a->logits_out (if
+ * set); train_mode selects dropout.  backward consumes d(log-probabilities) and must follow a train-mode
+ * forward on the same workspace. */
+int abd_largecnn_forward(abd_largecnn* net, const abd_largecnn_args* a, int train_mode, void* workspace,
+                         size_t workspace_bytes, abd_stream_t stream);
+int abd_largecnn_backward(abd_largecnn* net, const abd_largecnn_args* a, const float* dlogits, void* workspace,
+                          size_t workspace_bytes, abd_stream_t stream);
+/* forward, cross entropy on the log-probabilities (mean over the batch) with the ABD_METRICS_WORDS
+ * counters, backward, and abd_adam_f32 on the flat buffer when do_update; d(logits) in torch's
+ * log_softmax / nll_loss arithmetic as in abd_lstmattn_train_step.  labels are required (ABD_E_INVALID). */
+int abd_largecnn_train_step(abd_largecnn* net, const abd_largecnn_args* a, void* workspace,
+                            size_t workspace_bytes, abd_stream_t stream);
+/* eval forward (no dropout).  Writes the log-probabilities and, if labels != NULL, accumulates the
+ * counters like test(). */
+int abd_largecnn_eval(abd_largecnn* net, const float* x, int64_t batch, const float* params,
+                      const int64_t* labels, const int64_t* indicators, float* logits, int64_t* metrics,
+                      void* workspace, size_t workspace_bytes, abd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
