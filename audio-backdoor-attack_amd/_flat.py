@@ -1,4 +1,5 @@
-"""The flat-buffer engine shared by ``models_lstm.lstmwithattention`` and ``models_rnn.RNN``.
+"""The flat-buffer engine shared by ``models_lstm.lstmwithattention``, ``models_rnn.RNN``, ``models_largecnn.largecnn``
+and ``models_resnet.ResNet``.
 
 Both models keep their parameters in ONE flat device buffer in ``PARAM_ORDER`` (and their BatchNorm running
 statistics, if any, in a second one), drive a family of C entry points that differ only in their prefix
@@ -86,7 +87,8 @@ class FlatModule:
         """(index, BatchNorm module, its running_mean view, its running_var view) per RUNNING_ORDER entry."""
         o = 0
         for i, (name, c) in enumerate(self.RUNNING_ORDER):
-            yield i, getattr(self, name), eng.running[o:o + c], eng.running[o + c:o + 2 * c]
+            bn = self.get_submodule(name) if "." in name else getattr(self, name)   # ResNet's nested BatchNorms
+            yield i, bn, eng.running[o:o + c], eng.running[o + c:o + 2 * c]
             o += 2 * c
 
     def _bound(self, eng) -> bool:

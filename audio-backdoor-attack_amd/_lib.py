@@ -51,6 +51,10 @@ EXPORTS = (
     "abd_largecnn_tile_info", "abd_largecnn_linear_features", "abd_largecnn_workspace_bytes",
     "abd_largecnn_workspace_offset", "abd_largecnn_set_large_min_blocks", "abd_largecnn_forward",
     "abd_largecnn_backward", "abd_largecnn_train_step", "abd_largecnn_eval",
+    "abd_resnet_create", "abd_resnet_destroy", "abd_resnet_param_count", "abd_resnet_param_offsets",
+    "abd_resnet_running_count", "abd_resnet_running_offsets", "abd_resnet_tile_info", "abd_resnet_linear_features",
+    "abd_resnet_workspace_bytes", "abd_resnet_workspace_offset", "abd_resnet_forward", "abd_resnet_backward",
+    "abd_resnet_train_step", "abd_resnet_eval",
     "abd_profile_start", "abd_profile_start_every", "abd_profile_step", "abd_profile_stop",
 )
 
@@ -143,6 +147,19 @@ class LargeCnnArgs(C.Structure):
         ("mask1_in", C.c_void_p), ("mask2_in", C.c_void_p), ("seed", C.c_uint64), ("counter", C.c_uint64),
         ("mask1_out", C.c_void_p), ("mask2_out", C.c_void_p),
         ("logits_out", C.c_void_p), ("metrics", C.c_void_p), ("grad_scale", C.c_float), ("row_offset", C.c_int64),
+    ]
+
+
+class ResNetArgs(C.Structure):
+    """abd_resnet_args: abd_rnn_args plus the running statistics and num_batches_tracked."""
+    _fields_ = [
+        ("x", C.c_void_p), ("labels", C.c_void_p), ("indicators", C.c_void_p), ("batch", C.c_int64),
+        ("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("running", C.c_void_p), ("adam_step", C.c_int64),
+        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("do_update", C.c_int),
+        ("logits_out", C.c_void_p), ("metrics", C.c_void_p), ("grad_scale", C.c_float),
+        ("num_batches_tracked", C.c_void_p),
     ]
 
 
@@ -327,6 +344,20 @@ def _declare(lib):
         "abd_largecnn_backward": (i32, [vp, C.POINTER(LargeCnnArgs), vp, vp, sz, vp]),
         "abd_largecnn_train_step": (i32, [vp, C.POINTER(LargeCnnArgs), vp, sz, vp]),
         "abd_largecnn_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "abd_resnet_create": (i32, [i32, i32, i32, C.POINTER(vp)]),
+        "abd_resnet_destroy": (None, [vp]),
+        "abd_resnet_param_count": (i64, [vp]),
+        "abd_resnet_param_offsets": (i32, [vp, C.POINTER(i64)]),
+        "abd_resnet_running_count": (i64, [vp]),
+        "abd_resnet_running_offsets": (i32, [vp, C.POINTER(i64)]),
+        "abd_resnet_tile_info": (i32, [i32]),
+        "abd_resnet_linear_features": (i64, [i32, i32]),
+        "abd_resnet_workspace_bytes": (sz, [vp, i64]),
+        "abd_resnet_workspace_offset": (i64, [vp, i64, C.c_char_p]),
+        "abd_resnet_forward": (i32, [vp, C.POINTER(ResNetArgs), i32, vp, sz, vp]),
+        "abd_resnet_backward": (i32, [vp, C.POINTER(ResNetArgs), vp, vp, sz, vp]),
+        "abd_resnet_train_step": (i32, [vp, C.POINTER(ResNetArgs), vp, sz, vp]),
+        "abd_resnet_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "abd_profile_start": (i32, [C.c_ulonglong, i32]),
         "abd_profile_start_every": (i32, [C.c_ulonglong, i32, i32]),
         "abd_profile_step": (i32, []),

@@ -708,13 +708,13 @@ def _(x, labels, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracke
     return x.new_empty((x.shape[0], num_classes))
 
 
-# --------------------------------------------------------------------------- lstmwithattention, RNN, largecnn
+# --------------------------------------------------------------------------- lstmwithattention, RNN, largecnn, ResNet
 _FLAT_NETS: dict = {}
 
 
 def _flat_net(prefix: str, T: int, F: int, K: int):
-    """A cached libabd handle (prefix abd_lstmattn / abd_rnn / abd_largecnn) for one geometry: shapes only, no device
-    state."""
+    """A cached libabd handle (prefix abd_lstmattn / abd_rnn / abd_largecnn / abd_resnet) for one geometry: shapes only,
+    no device state."""
     key = (prefix, int(T), int(F), int(K))
     h = _FLAT_NETS.get(key)
     if h is None:
@@ -900,4 +900,53 @@ def largecnn_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor],
 @largecnn_train_step.register_fake
 def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, metrics, num_classes, adam_step, lr, beta1, beta2,
       eps, seed, counter, mask1=None, mask2=None):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+def _resnet_eval(x, params, running, num_classes, labels, indicators, metrics):
+    return _flat_eval("abd_resnet", "ResNet", x, params, (running,), num_classes, labels, indicators, metrics)
+
+
+@torch.library.custom_op("abd::resnet_eval", mutates_args=())
+def resnet_eval(x: Tensor, params: Tensor, running: Tensor, num_classes: int) -> Tensor:
+    """model.eval() forward of ResNet: (B, 1, H, W) -> logits (B, K); running BN statistics, nothing updated."""
+    return _resnet_eval(x, params, running, num_classes, None, None, None)
+
+
+@resnet_eval.register_fake
+def _(x, params, running, num_classes):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::resnet_eval_metrics", mutates_args=("metrics",))
+def resnet_eval_metrics(x: Tensor, params: Tensor, running: Tensor, num_classes: int, labels: Tensor,
+                        indicators: Optional[Tensor], metrics: Tensor) -> Tensor:
+    """The eval forward plus test()'s loss / accuracy / ASR counters accumulated into metrics (int64[8]);
+    returns the logits."""
+    return _resnet_eval(x, params, running, num_classes, labels, indicators, metrics)
+
+
+@resnet_eval_metrics.register_fake
+def _(x, params, running, num_classes, labels, indicators, metrics):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::resnet_train_step",
+                         mutates_args=("params", "grads", "exp_avg", "exp_avg_sq", "running", "num_batches_tracked",
+                                       "metrics"))
+def resnet_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor], params: Tensor, grads: Tensor,
+                      exp_avg: Tensor, exp_avg_sq: Tensor, running: Tensor, num_batches_tracked: Tensor,
+                      metrics: Tensor, num_classes: int, adam_step: int, lr: float, beta1: float, beta2: float,
+                      eps: float) -> Tensor:
+    """One fused train() iteration of ResNet on the device; returns the batch's logits (B, K).
+    adam_step >= 1 applies torch.optim.Adam (that step index); 0 leaves params untouched."""
+    a = L.ResNetArgs()
+    a.running, a.num_batches_tracked = running.data_ptr(), num_batches_tracked.data_ptr()
+    return _flat_train_step("abd_resnet", "ResNet", a, x, labels, indicators, params, grads, exp_avg, exp_avg_sq,
+                            metrics, num_classes, adam_step, lr, beta1, beta2, eps)
+
+
+@resnet_train_step.register_fake
+def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics, num_classes,
+      adam_step, lr, beta1, beta2, eps):
     return x.new_empty((x.shape[0], num_classes))

@@ -23,23 +23,28 @@ from .models import smallcnn, dropout_seed
 from .models_lstm import lstmwithattention
 from .models_rnn import RNN
 from .models_largecnn import largecnn, adopt, adoptable
+from . import models_resnet
+from .models_resnet import ResNet
 from .resident import resident_batches
 
 # the models whose train() / test() steps run on libabd
-ACCELERATED = (smallcnn, lstmwithattention, RNN, largecnn)
+ACCELERATED = (smallcnn, lstmwithattention, RNN, largecnn, ResNet)
 
 
 def accelerated(model):
-    """The model train() / test() drive: model itself, or, for a reference-built ``utils.models.largecnn``
-    instance (what the unmodified attack scripts hold), its adoption (models_largecnn.adopt: the same submodules
-    and Parameter objects under the abd class).  A module named largecnn of another structure raises AbdError."""
-    return adopt(model) if adoptable(model) else model
+    """The model train() / test() drive: model itself, or, for a reference-built ``utils.models.largecnn`` or
+    ``utils.models.ResNet`` instance (what the unmodified attack scripts hold), its adoption (models_largecnn.adopt /
+    models_resnet.adopt: the same submodules, Parameter objects and BatchNorm buffers under the abd class).  A module
+    named largecnn or ResNet of another structure raises AbdError."""
+    if adoptable(model):
+        return adopt(model)
+    return models_resnet.adopt(model) if models_resnet.adoptable(model) else model
 
 
 def require_smallcnn(model, what: str):
     """Raise AbdError unless model is the abd_amd smallcnn: the data-parallel / SyncBN trainer, the direct
     smallcnn step and the defences drive the abd_smallcnn_* entry points, whose handle and flat buffer layout
-    are smallcnn's own (lstmwithattention, RNN and largecnn -- adopted reference instances included -- have the
+    are smallcnn's own (lstmwithattention, RNN, largecnn and ResNet -- adopted reference instances included -- have the
     same Python surface but another layout)."""
     if not isinstance(model, smallcnn):
         raise L.AbdError(f"{what} runs the abd_amd smallcnn only, got {type(model).__name__}")
@@ -294,12 +299,31 @@ def largecnn_train_step(model: largecnn, x, labels, indicators, adam: AdamBindin
     return _flat_step(eng, a, x)
 
 
+def resnet_train_step(model: ResNet, x, labels, indicators, adam: AdamBinding | None, metrics: torch.Tensor | None,
+                      do_update=True, grad_scale=1.0, logits_out=None):
+    """One fused device step of ResNet (forward + CE on the logits + backward [+ Adam]) through the C ABI; the
+    running statistics and num_batches_tracked advance."""
+    model._check_input(x)
+    x = x.contiguous()
+    eng, a = _flat_step_args(model, x, labels, indicators, adam, metrics, do_update, grad_scale, logits_out)
+    eng.last_train_token = -1   # the step overwrites the workspace a pending autograd backward would read
+    return _flat_step(eng, a, x)
+
+
 def op_train_step(model: smallcnn | lstmwithattention, x, labels, indicators, adam: AdamBinding,
                   metrics: torch.Tensor):
     """train()'s per-batch step through the model's custom op, ``abd::smallcnn_train_step``,
-    ``abd::lstmattn_train_step``, ``abd::rnn_train_step`` or ``abd::largecnn_train_step`` (ops.py)."""
+    ``abd::lstmattn_train_step``, ``abd::rnn_train_step``, ``abd::largecnn_train_step`` or
+    ``abd::resnet_train_step`` (ops.py)."""
     from . import ops  # noqa: F401  (registers torch.ops.abd)
     eng = model.engine(x)
+    if isinstance(model, ResNet):
+        adam.step += 1
+        torch.ops.abd.resnet_train_step(
+            x, labels, indicators, eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, eng.running, eng.nbt, metrics,
+            eng.K, adam.step, adam.lr, adam.betas[0], adam.betas[1], adam.eps)
+        eng.last_train_token = -1
+        return
     if isinstance(model, largecnn):
         hm = model.step_masks(x.shape[0], x.device)
         adam.step += 1
@@ -356,7 +380,7 @@ def read_metrics(m: torch.Tensor):
 
 
 def _unsupported(model):
-    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn / lstmwithattention / RNN / largecnn + Adam + "
+    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn / lstmwithattention / RNN / largecnn / ResNet + Adam + "
                      f"CrossEntropyLoss hot path only; got {type(model).__name__} (other models and optimizers are out "
                      f"of scope, see DESIGN.md)")
 
@@ -396,6 +420,8 @@ def _eval_batches(model, loader, dev, dict_items):
             torch.ops.abd.rnn_eval_metrics(x, eng.params, eng.K, y, ind, metrics)
         elif isinstance(model, largecnn):
             torch.ops.abd.largecnn_eval_metrics(x, eng.params, eng.K, y, ind, metrics)
+        elif isinstance(model, ResNet):
+            torch.ops.abd.resnet_eval_metrics(x, eng.params, eng.running, eng.K, y, ind, metrics)
         elif isinstance(model, lstmwithattention):
             torch.ops.abd.lstmattn_eval_metrics(x, eng.params, eng.running, eng.K, y, ind, metrics)
         else:

@@ -994,6 +994,92 @@ int abd_largecnn_eval(abd_largecnn* net, const float* x, int64_t batch, const fl
                       const int64_t* labels, const int64_t* indicators, float* logits, int64_t* metrics,
                       void* workspace, size_t workspace_bytes, abd_stream_t stream);
 
+/* ------------------------------------------------------------------ ResNet
+ * Replaces utils/models.py:261-332 ResNet(ResidualBlock, [2, 2, 2], num_classes, linear_features): stem
+ * conv3x3(1->16) BN relu; layer1 two blocks 16->16; layer2 a stride-2 block 16->32 whose residual is a
+ * conv3x3 stride 2 + BN downsample, then a block 32->32; layer3 the same for 32->64 and 64->64; conv2d
+ * 1x1 64->64 stride (2, 1) with bias; AvgPool2d(4) (floor); fc on the (C, PH, PW) flatten.  A block is
+ * relu(bn2(conv2(relu(bn1(conv1(x))))) + residual).  Every 3x3 conv has padding 1 and no bias.  Input
+ * (B, 1, H, W) fp32; raw logits out; the loss is cross entropy on them.
+ *
+ * Parameters live in ONE flat fp32 buffer in named_parameters() order, 49 tensors: for each of the
+ * fifteen conv + BatchNorm units (conv/bn, layer1.0.conv1/bn1, layer1.0.conv2/bn2, layer1.1.., layer2.0
+ * conv1/bn1, conv2/bn2, downsample.0/.1, layer2.1.., layer3 alike) the conv weight (Cout, Cin, 3, 3), the
+ * BN weight and the BN bias; then conv2d.weight, conv2d.bias, fc.weight, fc.bias.  running: for each unit
+ * in that order running_mean[Cout] then running_var[Cout], 1120 floats; num_batches_tracked: int64[15].
+ *
+ * Every product is fp32.  Activations are channels-last (B, H, W, C) in the workspace.  The fourteen convs
+ * behind the stem and their data and weight gradients are implicit GEMMs on v_mfma_f32_16x16x4_f32 (no
+ * im2col buffer), stride 1 and 2; the weight gradients' pixel reduction is cut into slices summed in slice
+ * order; the stem is a direct kernel.  BatchNorm takes per-block sums in double, combined in block order
+ * and in double (biased variance, eps 1e-5; running statistics with momentum 0.1 and the unbiased
+ * variance).  There are no float atomics and two calls on equal inputs give bit-equal results.  The entry
+ * points allocate nothing, never synchronise and take nothing from host memory but their arguments. */
+typedef struct abd_resnet abd_resnet;
+
+/* abd_rnn_args plus the running statistics */
+typedef struct abd_resnet_args {
+  const float* x;            /* (B,1,H,W)                                      */
+  const int64_t* labels;     /* (B)                                            */
+  const int64_t* indicators; /* (B) poison indicator, NULL = none              */
+  int64_t batch;
+  float* params;             /* flat                                           */
+  float* grads;              /* flat (written)                                 */
+  float* exp_avg;            /* flat Adam m                                    */
+  float* exp_avg_sq;         /* flat Adam v                                    */
+  float* running;            /* 1120 floats; NULL in a train-mode call leaves
+                              * the running statistics alone                   */
+  int64_t adam_step;         /* step index after increment (1-based)           */
+  float lr, beta1, beta2, eps;
+  int do_update;             /* 0: forward/backward only (grads), 1: + Adam    */
+  float* logits_out;         /* optional (B,K)                                 */
+  int64_t* metrics;          /* optional ABD_METRICS_WORDS accumulators        */
+  float grad_scale;          /* multiplies the loss gradient and weights
+                              * metrics[0]'s batch-mean loss                   */
+  int64_t* num_batches_tracked; /* optional int64[15], += 1 per train forward  */
+} abd_resnet_args;
+
+/* fc's inputs for an (H, W) input: 64 * (H4 / 4) * (W3 / 4) with H2 = (H - 1) / 2 + 1, H3 = (H2 - 1) / 2 + 1,
+ * H4 = (H3 - 1) / 2 + 1 and W3 alike, in integer division; -1 below 25 x 13 (the pool has no window) */
+int64_t abd_resnet_linear_features(int H, int W);
+/* ABD_E_UNSUPPORTED for H < 25 or W < 13, a side above 4096, a geometry whose element indices leave 32
+ * bits, num_classes outside [1, 4096] */
+int abd_resnet_create(int H, int W, int num_classes, abd_resnet** net);
+void abd_resnet_destroy(abd_resnet* net);
+int64_t abd_resnet_param_count(const abd_resnet* net);
+int abd_resnet_param_offsets(const abd_resnet* net, int64_t* offsets /* 50 */);
+int64_t abd_resnet_running_count(const abd_resnet* net);
+/* offsets[u]: unit u's running_mean inside running (its running_var follows); offsets[15] = the count */
+int abd_resnet_running_offsets(const abd_resnet* net, int64_t* offsets /* 16 */);
+/* kernel geometry (tests): 0 rows of a GEMM block tile, 1 the K-step, 2 least pixels of a weight-gradient
+ * slice, 3 most slices, 4 least pixels of a BatchNorm partial block, 5 most such blocks; -1 otherwise */
+int abd_resnet_tile_info(int what);
+size_t abd_resnet_workspace_bytes(const abd_resnet* net, int64_t batch);
+/* Byte offset of a saved map inside the workspace (tests), -1 for an unknown name.  For unit u = 0..14:
+ * z<u> the conv output, a<u> what the unit's BatchNorm pass wrote (after the residual add and the relu where
+ * the unit has them), s<u> the batch mean[Cout] then 1 / sqrt(var + eps)[Cout]; all maps channels-last.
+ * sub ((B, H4, W3, 64): the rows conv2d reads), c2 (conv2d's output), pool ((B, 64, PH, PW): fc's input row
+ * in the reference's flatten order), logits dlogits rowinfo. */
+int64_t abd_resnet_workspace_offset(const abd_resnet* net, int64_t batch, const char* name);
+/* forward keeps every map in the workspace and writes the logits to a->logits_out (if set); train_mode
+ * selects batch statistics (running statistics and num_batches_tracked updated when given) vs the running
+ * statistics (required then).  backward consumes d(logits) and must follow a train-mode forward on the same
+ * workspace. */
+int abd_resnet_forward(abd_resnet* net, const abd_resnet_args* a, int train_mode, void* workspace,
+                       size_t workspace_bytes, abd_stream_t stream);
+int abd_resnet_backward(abd_resnet* net, const abd_resnet_args* a, const float* dlogits, void* workspace,
+                        size_t workspace_bytes, abd_stream_t stream);
+/* forward, cross entropy on the logits (mean over the batch) with the ABD_METRICS_WORDS counters, backward,
+ * and abd_adam_f32 on the flat buffer when do_update; d(logits) in torch's log_softmax / nll_loss
+ * arithmetic as in abd_lstmattn_train_step.  labels are required (ABD_E_INVALID). */
+int abd_resnet_train_step(abd_resnet* net, const abd_resnet_args* a, void* workspace, size_t workspace_bytes,
+                          abd_stream_t stream);
+/* eval forward: running statistics, nothing updated.  Writes the logits and, if labels != NULL,
+ * accumulates the counters like test(). */
+int abd_resnet_eval(abd_resnet* net, const float* x, int64_t batch, const float* params, const float* running,
+                    const int64_t* labels, const int64_t* indicators, float* logits, int64_t* metrics,
+                    void* workspace, size_t workspace_bytes, abd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
