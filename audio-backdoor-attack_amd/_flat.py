@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 
 import torch
+import torch.nn as nn
 
 from . import _lib as L
 
@@ -78,6 +79,36 @@ class FlatModule:
 
     RUNNING_ORDER = ()
     BACKWARD_CONSUMES = False
+    NAME = "model"    # the display name in messages
+    TRANSIENT = ()    # attributes that live for one launch and are not pickled
+
+    def set_gemm_precision(self, precision: str):
+        """fp32 products only ('f32', or 'f32split' which names the same accuracy class): 'bf16' raises
+        AbdError."""
+        if precision not in L.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(L.PRECISIONS)}, got {precision!r}")
+        if precision == "bf16":
+            raise L.AbdError(f"{self.NAME} has no bf16 mode: every product is fp32 (DESIGN.md §5)")
+        return self
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_engine"] = None
+        for k in self.TRANSIENT:
+            st.pop(k, None)
+        return st
+
+    def _check_input(self, x):
+        L.require_device(x, f"{self.NAME} input")
+        if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
+            raise ValueError(f"{self.NAME} expects (B, 1, H, W) float32")
+
+    def forward(self, x):
+        self._check_input(x)
+        self.engine(x)
+        if self.training and torch.is_grad_enabled():
+            return FlatFunction.apply(x, self, *self._param_list())
+        return self.hip_forward(x, train=self.training)
 
     def _param_list(self):
         d = dict(self.named_parameters())
@@ -170,3 +201,52 @@ class FlatFunction(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         gs = ctx.model.hip_backward(x, dl, ctx.token)
         return (None, None, *[g.view(s).clone() for g, s in zip(gs, ctx.shapes)])
+
+
+# ------------------------------------------------------------------ adoption of a reference-built instance
+def pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def sub(m: nn.Module, name: str):
+    """m's submodule at the dotted path, or None."""
+    try:
+        return m.get_submodule(name)
+    except AttributeError:
+        return None
+
+
+def check_conv3x3(module, name, cin, cout, stride, bias, refuse):
+    """module's submodule `name` must be Conv2d(cin, cout, 3, stride, padding 1) with or without a bias, nothing
+    else set; refuse(why) raises."""
+    c = sub(module, name)
+    if not isinstance(c, nn.Conv2d):
+        refuse(f"{name} is missing or no Conv2d")
+    if ((c.in_channels, c.out_channels) != (cin, cout) or pair(c.kernel_size) != (3, 3)
+            or pair(c.stride) != (stride, stride) or c.padding not in (1, (1, 1)) or pair(c.dilation) != (1, 1)
+            or c.groups != 1 or (c.bias is not None) != bias or c.padding_mode != "zeros"):
+        refuse(f"{name} is not Conv2d({cin}, {cout}, 3, stride {stride}, padding 1, {'bias' if bias else 'no bias'})")
+
+
+def adoptable(module, cls) -> bool:
+    """A module cls's adopt would look at: named like cls, but not cls itself."""
+    return isinstance(module, nn.Module) and not isinstance(module, cls) and type(module).__name__ == cls.__name__
+
+
+def adopt_into(cls, module, children, cache, check, unchanged, fill=None):
+    """The common body of the models' adopt(): the cached adoption of `module` while unchanged(got, module) holds;
+    else check(module) (which raises on a foreign structure) and a new cls whose `children` ARE module's own
+    (fill(name) stands in for one that module lacks), in module's train / eval state, cached weakly."""
+    got = cache.get(module)
+    if got is not None and unchanged(got, module):
+        return got
+    check(module)
+    new = cls.__new__(cls)
+    nn.Module.__init__(new)
+    for name in children:
+        child = getattr(module, name, None)
+        new.add_module(name, child if fill is None or isinstance(child, nn.Module) else fill(name))
+    new._init_abd()
+    new.train(module.training)
+    cache[module] = new
+    return new

@@ -5,7 +5,8 @@
 //
 // Activations are channels-last (B, H, W, C) in the workspace; only the pooled 256-channel map is written in
 // the reference's (B, C, H, W) order, which is fc1's input row.  conv2..conv5 are implicit GEMMs on
-// v_mfma_f32_32x32x2_f32 (conv_gemm_kernel, rnn.hip's LDS-tiled block with a pixel gather in one loader):
+// v_mfma_f32_32x32x2_f32 (conv_gemm_kernel: the LDS-tiled block of gemm_tiled.inc written out with a pixel gather
+// in each loader; handing the gathers to the shared body as a policy compiled to a slower schedule):
 //   forward        M = pixels, N = Cout, K = 9 Cin; A = the nine shifted pixel rows, zero outside the image
 //   data gradient  M = pixels, N = Cin,  K = 9 Cout; the same gather with the tap offsets negated
 //   weight grad    M = Cout,   N = Cin,  K = pixels, one z-slab per (slice, tap); B = the shifted pixel rows
@@ -33,8 +34,6 @@ struct abd_largecnn {
 namespace {
 
 constexpr int kT = 256;
-constexpr int kBK = 32;            // K-step of the tiled kernel
-constexpr int kSmallTile = 64, kLargeTile = 128;
 constexpr int kLargeMinBlocks = 96;  // below this many 128 x 128 blocks the 64 x 64 tile fills more CUs
 constexpr int kSliceRows = 256;    // least pixels of one weight-gradient slice
 constexpr int kMaxSlices = 16;
@@ -52,9 +51,8 @@ enum { P_C1W, P_C1B, P_C2W, P_C2B, P_C3W, P_C3B, P_C4W, P_C4B, P_C5W, P_C5B, P_F
        P_F3B, P_COUNT };
 
 // GemmArgs and its three forms, the host helpers; colsum_kernel, ce_kernel, metrics_kernel
-#include "lstm_common.inc"
-
-typedef float f16v __attribute__((ext_vector_type(16)));
+#include "net_common.inc"
+#include "gemm_tiled.inc"   // kBK, the tile sizes, f16v and launch_tiled
 
 // the dropout hash of the smallcnn kernels: keep with probability 1 - p
 __device__ __forceinline__ bool keep_hash(uint64_t seed, uint64_t stream, uint64_t idx, float p) {
@@ -529,7 +527,6 @@ struct Fwd {
 inline unsigned blocks(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
 
 int launch_gemm(const Ctx& c, ConvGemm cg, int nz = 1) {
-  hipStream_t s = c.s;
   GemmArgs& g = cg.g;
   if (g.M <= 0 || g.N <= 0) return ABD_OK;
   if (cg.mode != 2) g.kchunk = std::max(g.K, 1);
@@ -537,16 +534,7 @@ int launch_gemm(const Ctx& c, ConvGemm cg, int nz = 1) {
     cg.invH = 1.0f / (float)cg.H;
     cg.invW = 1.0f / (float)cg.W;
   }
-  const int64_t large = (int64_t)((g.M + kLargeTile - 1) / kLargeTile) * ((g.N + kLargeTile - 1) / kLargeTile) * nz;
-  if (large >= c.n->large_min_blocks) {
-    dim3 grid((g.M + kLargeTile - 1) / kLargeTile, (g.N + kLargeTile - 1) / kLargeTile, nz);
-    conv_gemm_kernel<2, 2><<<grid, kT, 0, s>>>(cg);
-  } else {
-    dim3 grid((g.M + kSmallTile - 1) / kSmallTile, (g.N + kSmallTile - 1) / kSmallTile, nz);
-    conv_gemm_kernel<1, 1><<<grid, kT, 0, s>>>(cg);
-  }
-  ABD_LAUNCH_CHECK();
-  return ABD_OK;
+  return launch_tiled(c.s, g.M, g.N, nz, c.n->large_min_blocks, conv_gemm_kernel<1, 1>, conv_gemm_kernel<2, 2>, cg);
 }
 
 int launch_gemm(const Ctx& c, const GemmArgs& g) {
@@ -812,19 +800,13 @@ int abd_largecnn_backward(abd_largecnn* net, const abd_largecnn_args* a, const f
 
 int abd_largecnn_train_step(abd_largecnn* net, const abd_largecnn_args* a, void* workspace, size_t workspace_bytes,
                             abd_stream_t stream) {
-  ABD_CHECK(a != nullptr && a->x && a->grads, ABD_E_INVALID, "NULL x / grads");
-  ABD_CHECK(a->labels != nullptr, ABD_E_INVALID, "train_step needs labels");
-  ABD_CHECK(!a->do_update || (a->exp_avg && a->exp_avg_sq && a->adam_step >= 1), ABD_E_INVALID,
-            "do_update needs the Adam moments and adam_step >= 1");
+  if (int rc = check_train_args(a)) return rc;
   Ctx c;
   if (int rc = make_ctx(net, a->batch, a->params, a->grads, workspace, workspace_bytes, stream, &c)) return rc;
   if (int rc = run_forward(c, fwd_of(a, 1), true)) return rc;
   if (int rc = run_loss(c, a->labels, a->indicators, true, a->grad_scale, a->logits_out, a->metrics)) return rc;
   if (int rc = run_backward(c, a->x, c.at<float>(c.L.dlogits))) return rc;
-  if (a->do_update)
-    return abd_adam_f32(a->params, a->grads, a->exp_avg, a->exp_avg_sq, net->off[P_COUNT], a->adam_step, a->lr,
-                        a->beta1, a->beta2, a->eps, stream);
-  return ABD_OK;
+  return adam_tail(a, net->off[P_COUNT], stream);
 }
 
 int abd_largecnn_eval(abd_largecnn* net, const float* x, int64_t batch, const float* params, const int64_t* labels,

@@ -1230,11 +1230,9 @@ int abd_lstmattn_backward(abd_lstmattn* net, const abd_lstmattn_args* a, const f
 int abd_lstmattn_train_step(abd_lstmattn* net, const abd_lstmattn_args* a, void* workspace, size_t workspace_bytes,
                             abd_stream_t stream) {
   ABD_CHECK(a != nullptr && a->x && a->running && a->grads, ABD_E_INVALID, "NULL x / running / grads");
-  ABD_CHECK(a->labels != nullptr, ABD_E_INVALID, "train_step needs labels");
+  if (int rc = check_train_args(a)) return rc;
   ABD_CHECK(net == nullptr || a->batch * net->T * net->F > 1, ABD_E_INVALID,
             "train-mode BatchNorm needs more than one value per channel (B*T*F = 1)");
-  ABD_CHECK(!a->do_update || (a->exp_avg && a->exp_avg_sq && a->adam_step >= 1), ABD_E_INVALID,
-            "do_update needs the Adam moments and adam_step >= 1");
   Ctx c;
   if (int rc = make_ctx(net, a->batch, a->params, a->grads, workspace, workspace_bytes, stream, &c)) return rc;
   const Fwd f{a->x, a->running, a->num_batches_tracked, 1, a->mask_in, a->mask_out, a->seed, a->counter,
@@ -1242,10 +1240,7 @@ int abd_lstmattn_train_step(abd_lstmattn* net, const abd_lstmattn_args* a, void*
   if (int rc = run_forward(c, f)) return rc;
   if (int rc = run_ce(c, a->labels, a->indicators, true, a->grad_scale, a->logits_out, a->metrics)) return rc;
   if (int rc = run_backward(c, a->x, c.at<float>(c.L.dlogits))) return rc;
-  if (a->do_update)
-    return abd_adam_f32(a->params, a->grads, a->exp_avg, a->exp_avg_sq, net->off[P_COUNT], a->adam_step, a->lr,
-                        a->beta1, a->beta2, a->eps, stream);
-  return ABD_OK;
+  return adam_tail(a, net->off[P_COUNT], stream);
 }
 
 int abd_lstmattn_eval(abd_lstmattn* net, const float* x, int64_t batch, const float* params, const float* running,

@@ -1,5 +1,6 @@
-// Fixed-order column sums, cross entropy and the ABD_METRICS_WORDS counters, shared by lstm_attn.hip and
-// rnn.hip.  Included by lstm_common.inc, inside each file's anonymous namespace, after abd_common.h.
+// Fixed-order column sums, cross entropy and the ABD_METRICS_WORDS counters, shared by lstm_attn.hip, rnn.hip,
+// largecnn.hip and resnet.hip.  Included by net_common.inc, inside each file's anonymous namespace, after
+// abd_common.h.
 
 constexpr int kRedT = 256;   // threads of colsum_kernel / metrics_kernel
 

@@ -68,7 +68,7 @@ constexpr Block kBlock[6] = {{0, 1, 2, -1}, {2, 3, 4, -1}, {4, 5, 6, 7}, {6, 8, 
 enum { P_C2DW = 3 * kUnits, P_C2DB, P_FCW, P_FCB, P_COUNT };
 
 // GemmArgs and its three forms, the host helpers; colsum_kernel, ce_kernel, metrics_kernel
-#include "lstm_common.inc"
+#include "net_common.inc"
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 
@@ -909,10 +909,7 @@ int abd_resnet_backward(abd_resnet* net, const abd_resnet_args* a, const float* 
 
 int abd_resnet_train_step(abd_resnet* net, const abd_resnet_args* a, void* workspace, size_t workspace_bytes,
                           abd_stream_t stream) {
-  ABD_CHECK(a != nullptr && a->x && a->grads, ABD_E_INVALID, "NULL x / grads");
-  ABD_CHECK(a->labels != nullptr, ABD_E_INVALID, "train_step needs labels");
-  ABD_CHECK(!a->do_update || (a->exp_avg && a->exp_avg_sq && a->adam_step >= 1), ABD_E_INVALID,
-            "do_update needs the Adam moments and adam_step >= 1");
+  if (int rc = check_train_args(a)) return rc;
   Ctx c;
   if (int rc = make_rctx(net, a->batch, a->params, a->grads, a->running, a->num_batches_tracked, workspace,
                         workspace_bytes, stream, &c))
@@ -920,10 +917,7 @@ int abd_resnet_train_step(abd_resnet* net, const abd_resnet_args* a, void* works
   if (int rc = run_forward(c, a->x, 1)) return rc;
   if (int rc = run_ce(c, a->labels, a->indicators, true, a->grad_scale, a->logits_out, a->metrics)) return rc;
   if (int rc = run_backward(c, a->x, c.at<float>(c.L.dlogits))) return rc;
-  if (a->do_update)
-    return abd_adam_f32(a->params, a->grads, a->exp_avg, a->exp_avg_sq, net->off[P_COUNT], a->adam_step, a->lr,
-                        a->beta1, a->beta2, a->eps, stream);
-  return ABD_OK;
+  return adam_tail(a, net->off[P_COUNT], stream);
 }
 
 int abd_resnet_eval(abd_resnet* net, const float* x, int64_t batch, const float* params, const float* running,

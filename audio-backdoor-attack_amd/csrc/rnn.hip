@@ -28,10 +28,8 @@ constexpr int kT = 256;
 constexpr int kHid = 768;          // LSTM hidden size
 constexpr int kGates = 4 * kHid;   // gate rows, torch order i f g o
 constexpr int kLayers = 3;
-constexpr int kBK = 32;            // K-step of the tiled kernels
 constexpr int kRecRows = 32;       // batch rows of one recurrent workgroup
 constexpr int kRecUnits = 32;      // hidden units of one recurrent workgroup
-constexpr int kSmallTile = 64, kLargeTile = 128;
 constexpr int kLargeMinBlocks = 96;  // below this many 128 x 128 blocks the 64 x 64 tile fills more CUs
 constexpr int kSliceRows = 256;    // least rows of one weight-gradient slice
 constexpr int kMaxSlices = 8;
@@ -41,8 +39,7 @@ enum { P_FCW = 4 * kLayers, P_FCB, P_COUNT };
 
 // backward cell, GemmArgs and its three forms, the host helpers; colsum_kernel, ce_kernel, metrics_kernel
 #include "lstm_common.inc"
-
-typedef float f16v __attribute__((ext_vector_type(16)));
+#include "gemm_tiled.inc"   // kBK, the tile sizes, f16v and launch_tiled
 
 // ------------------------------------------------------------------ LDS-tiled fp32 MFMA GEMM (GemmArgs)
 // An operand tile in LDS: [row][kBK + 1] when k is the contiguous index in memory, [k][rows + 32] when
@@ -289,16 +286,7 @@ int launch_gemm(hipStream_t s, GemmArgs g, int ksplit = 1) {
   if (g.M <= 0 || g.N <= 0) return ABD_OK;
   ksplit = std::max(1, ksplit);
   if (ksplit == 1) g.kchunk = std::max(g.K, 1);
-  const int64_t large = (int64_t)((g.M + kLargeTile - 1) / kLargeTile) * ((g.N + kLargeTile - 1) / kLargeTile) * ksplit;
-  if (large >= kLargeMinBlocks) {
-    dim3 grid((g.M + kLargeTile - 1) / kLargeTile, (g.N + kLargeTile - 1) / kLargeTile, ksplit);
-    gemm_tiled_kernel<2, 2><<<grid, kT, 0, s>>>(g);
-  } else {
-    dim3 grid((g.M + kSmallTile - 1) / kSmallTile, (g.N + kSmallTile - 1) / kSmallTile, ksplit);
-    gemm_tiled_kernel<1, 1><<<grid, kT, 0, s>>>(g);
-  }
-  ABD_LAUNCH_CHECK();
-  return ABD_OK;
+  return launch_tiled(s, g.M, g.N, ksplit, kLargeMinBlocks, gemm_tiled_kernel<1, 1>, gemm_tiled_kernel<2, 2>, g);
 }
 
 // out[cols] = column sums of A; two fixed-order stages past kColsumRows rows
@@ -493,19 +481,13 @@ int abd_rnn_backward(abd_rnn* net, const abd_rnn_args* a, const float* dlogits, 
 
 int abd_rnn_train_step(abd_rnn* net, const abd_rnn_args* a, void* workspace, size_t workspace_bytes,
                        abd_stream_t stream) {
-  ABD_CHECK(a != nullptr && a->x && a->grads, ABD_E_INVALID, "NULL x / grads");
-  ABD_CHECK(a->labels != nullptr, ABD_E_INVALID, "train_step needs labels");
-  ABD_CHECK(!a->do_update || (a->exp_avg && a->exp_avg_sq && a->adam_step >= 1), ABD_E_INVALID,
-            "do_update needs the Adam moments and adam_step >= 1");
+  if (int rc = check_train_args(a)) return rc;
   Ctx c;
   if (int rc = make_ctx(net, a->batch, a->params, a->grads, workspace, workspace_bytes, stream, &c)) return rc;
   if (int rc = run_forward(c, a->x)) return rc;
   if (int rc = run_ce(c, a->labels, a->indicators, true, a->grad_scale, a->logits_out, a->metrics)) return rc;
   if (int rc = run_backward(c, a->x, c.at<float>(c.L.dlogits))) return rc;
-  if (a->do_update)
-    return abd_adam_f32(a->params, a->grads, a->exp_avg, a->exp_avg_sq, net->off[P_COUNT], a->adam_step, a->lr,
-                        a->beta1, a->beta2, a->eps, stream);
-  return ABD_OK;
+  return adam_tail(a, net->off[P_COUNT], stream);
 }
 
 int abd_rnn_eval(abd_rnn* net, const float* x, int64_t batch, const float* params, const int64_t* labels,

@@ -60,6 +60,7 @@ class _Engine(_flat.FlatEngine):
 class largecnn(_flat.FlatModule, nn.Module):
     """Reference-compatible largecnn whose forward/backward run on libabd (HIP)."""
 
+    NAME, TRANSIENT = "largecnn", ("_host_masks",)
     PARAM_ORDER, ARGS, ENGINE = PARAM_ORDER, L.LargeCnnArgs, _Engine
     BACKWARD_ORDER = ("largecnn backward must directly follow its train-mode forward (activations live in the shared "
                       "workspace)")
@@ -90,15 +91,6 @@ class largecnn(_flat.FlatModule, nn.Module):
         self.dropout_source = "device"
 
     # ------------------------------------------------------------------ settings
-    def set_gemm_precision(self, precision: str):
-        """fp32 products only ('f32', or 'f32split' which names the same accuracy class): 'bf16' raises
-        AbdError."""
-        if precision not in L.PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(L.PRECISIONS)}, got {precision!r}")
-        if precision == "bf16":
-            raise L.AbdError("largecnn has no bf16 mode: every product is fp32 (DESIGN.md §5)")
-        return self
-
     def set_dropout_source(self, source: str):
         """'device' (default): the keep-masks come from the counter-based hash on the GPU.  'torch_cpu':
         bernoulli_(0.5) on (B, 256) then (B, 128) from the global CPU generator, as the reference's CPU forward
@@ -124,12 +116,6 @@ class largecnn(_flat.FlatModule, nn.Module):
             if k not in self.__dict__:
                 self.__dict__[k] = v
 
-    def __getstate__(self):
-        st = self.__dict__.copy()
-        st["_engine"] = None
-        st.pop("_host_masks", None)
-        return st
-
     # ------------------------------------------------------------------ binding
     def engine(self, x: torch.Tensor) -> _Engine:
         """Bind (or re-bind) the parameters to the flat device buffer for x's geometry."""
@@ -145,18 +131,6 @@ class largecnn(_flat.FlatModule, nn.Module):
         return eng
 
     # ------------------------------------------------------------------ launches
-    def _check_input(self, x):
-        L.require_device(x, "largecnn input")
-        if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
-            raise ValueError("largecnn expects (B, 1, H, W) float32")
-
-    def forward(self, x):
-        self._check_input(x)
-        self.engine(x)
-        if self.training and torch.is_grad_enabled():
-            return _flat.FlatFunction.apply(x, self, *self._param_list())
-        return self.hip_forward(x, train=self.training)
-
     def hip_forward(self, x, train: bool, seed: int | None = None, masks=None, masks_out=None):
         """The log-probabilities.  train: dropout on, every activation kept in the engine's workspace for
         hip_backward; masks: (mask1 (B, 256), mask2 (B, 128)) uint8 keep-masks in place of the hash."""
@@ -192,30 +166,20 @@ class largecnn(_flat.FlatModule, nn.Module):
 _ADOPTED: "weakref.WeakKeyDictionary[nn.Module, largecnn]" = weakref.WeakKeyDictionary()
 
 
-def _pair(v):
-    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-
-
 def _refuse(why: str):
     raise L.AbdError(f"not the reference's largecnn: {why}")
 
 
 def _check_structure(m: nn.Module):
     for name, cin, cout in CONVS:
-        c = getattr(m, name, None)
-        if not isinstance(c, nn.Conv2d):
-            _refuse(f"{name} is missing or no Conv2d")
-        if ((c.in_channels, c.out_channels) != (cin, cout) or _pair(c.kernel_size) != (3, 3)
-                or _pair(c.stride) != (1, 1) or c.padding not in (1, (1, 1)) or _pair(c.dilation) != (1, 1)
-                or c.groups != 1 or c.bias is None or c.padding_mode != "zeros"):
-            _refuse(f"{name} is not Conv2d({cin}, {cout}, 3, stride 1, padding 1, bias)")
+        _flat.check_conv3x3(m, name, cin, cout, 1, True, _refuse)
     for name, k, s in (("pool1", 2, 2), ("pool2", 2, 2), ("pool3", 3, 2)):
         p = getattr(m, name, None)
         if not isinstance(p, nn.MaxPool2d):
             _refuse(f"{name} is missing or no MaxPool2d")
         stride = p.stride if p.stride is not None else p.kernel_size
-        if (_pair(p.kernel_size) != (k, k) or _pair(stride) != (s, s) or _pair(p.padding) != (0, 0)
-                or _pair(p.dilation) != (1, 1) or p.ceil_mode or p.return_indices):
+        if (_flat.pair(p.kernel_size) != (k, k) or _flat.pair(stride) != (s, s) or _flat.pair(p.padding) != (0, 0)
+                or _flat.pair(p.dilation) != (1, 1) or p.ceil_mode or p.return_indices):
             _refuse(f"{name} is not MaxPool2d({k}, stride {s})")
     for name in ("fc1", "fc2", "fc3"):
         f = getattr(m, name, None)
@@ -245,23 +209,14 @@ def adopt(module: nn.Module) -> largecnn:
     ``forward`` still works.  One adoption per instance (a weak cache; the instance itself is not touched)."""
     if isinstance(module, largecnn):
         return module
-    if not isinstance(module, nn.Module) or type(module).__name__ != "largecnn":
+    if not adoptable(module):
         _refuse(f"got {type(module).__name__}")
-    got = _ADOPTED.get(module)
-    if got is not None and all(getattr(got, n) is getattr(module, n, None) for n in CHILDREN if n != "flat"):
-        return got
-    _check_structure(module)
-    new = largecnn.__new__(largecnn)
-    nn.Module.__init__(new)
-    for name in CHILDREN:
-        child = getattr(module, name, None)
-        new.add_module(name, child if isinstance(child, nn.Module) else nn.Flatten())
-    new._init_abd()
-    new.train(module.training)
-    _ADOPTED[module] = new
-    return new
+    return _flat.adopt_into(
+        largecnn, module, CHILDREN, _ADOPTED, _check_structure,
+        lambda got, m: all(getattr(got, n) is getattr(m, n, None) for n in CHILDREN if n != "flat"),
+        fill=lambda name: nn.Flatten())   # the reference's forward flattens with view(); only `flat` may be missing
 
 
 def adoptable(module) -> bool:
     """A module ``adopt`` would look at: named largecnn, but not this package's class."""
-    return isinstance(module, nn.Module) and not isinstance(module, largecnn) and type(module).__name__ == "largecnn"
+    return _flat.adoptable(module, largecnn)

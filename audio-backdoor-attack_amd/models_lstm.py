@@ -52,6 +52,7 @@ class _Engine(_flat.FlatEngine):
 class lstmwithattention(_flat.FlatModule, nn.Module):
     """Reference-compatible lstmwithattention whose forward/backward run on libabd (HIP)."""
 
+    NAME, TRANSIENT = "lstmwithattention", ("_host_mask",)
     PARAM_ORDER, RUNNING_ORDER, ARGS, ENGINE = PARAM_ORDER, RUNNING_ORDER, L.LstmAttnArgs, _Engine
     BACKWARD_ORDER = ("lstmwithattention backward must directly follow its train-mode forward (activations live in "
                       "the shared workspace)")
@@ -109,12 +110,6 @@ class lstmwithattention(_flat.FlatModule, nn.Module):
             if k not in self.__dict__:
                 self.__dict__[k] = v
 
-    def __getstate__(self):
-        st = self.__dict__.copy()
-        st["_engine"] = None
-        st.pop("_host_mask", None)
-        return st
-
     # ------------------------------------------------------------------ binding
     def engine(self, x: torch.Tensor) -> _Engine:
         """Bind (or re-bind) the parameters to flat device buffers for x's geometry."""
@@ -133,13 +128,6 @@ class lstmwithattention(_flat.FlatModule, nn.Module):
         L.require_device(x, "lstmwithattention input")
         if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
             raise ValueError("lstmwithattention expects (B, 1, T, n_mfcc) float32")
-
-    def forward(self, x):
-        self._check_input(x)
-        self.engine(x)
-        if self.training and torch.is_grad_enabled():
-            return _flat.FlatFunction.apply(x, self, *self._param_list())
-        return self.hip_forward(x, train=self.training)
 
     def hip_forward(self, x, train: bool, seed: int | None = None, mask=None, mask_out=None):
         eng = self.engine(x)

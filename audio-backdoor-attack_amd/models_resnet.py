@@ -106,6 +106,7 @@ class _Engine(_flat.FlatEngine):
 class ResNet(_flat.FlatModule, nn.Module):
     """Reference-compatible ResNet(ResidualBlock, [2, 2, 2], ...) whose forward/backward run on libabd (HIP)."""
 
+    NAME = "ResNet"
     PARAM_ORDER, RUNNING_ORDER, ARGS, ENGINE = PARAM_ORDER, RUNNING_ORDER, L.ResNetArgs, _Engine
     BACKWARD_ORDER = ("ResNet backward must directly follow its train-mode forward (activations live in the shared "
                       "workspace)")
@@ -143,26 +144,12 @@ class ResNet(_flat.FlatModule, nn.Module):
         self.gemm_precision = "f32"
 
     # ------------------------------------------------------------------ settings
-    def set_gemm_precision(self, precision: str):
-        """fp32 products only ('f32', or 'f32split' which names the same accuracy class): 'bf16' raises
-        AbdError."""
-        if precision not in L.PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(L.PRECISIONS)}, got {precision!r}")
-        if precision == "bf16":
-            raise L.AbdError("ResNet has no bf16 mode: every product is fp32 (DESIGN.md §5)")
-        return self
-
     def __setstate__(self, state):
         # also the target of reference-format checkpoints (training.reference_pickle_object)
         super().__setstate__(state)
         for k, v in (("_engine", None), ("gemm_precision", "f32")):
             if k not in self.__dict__:
                 self.__dict__[k] = v
-
-    def __getstate__(self):
-        st = self.__dict__.copy()
-        st["_engine"] = None
-        return st
 
     # ------------------------------------------------------------------ binding
     def engine(self, x: torch.Tensor) -> _Engine:
@@ -175,18 +162,6 @@ class ResNet(_flat.FlatModule, nn.Module):
         return self._bind(H, W, x.device)
 
     # ------------------------------------------------------------------ launches
-    def _check_input(self, x):
-        L.require_device(x, "ResNet input")
-        if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
-            raise ValueError("ResNet expects (B, 1, H, W) float32")
-
-    def forward(self, x):
-        self._check_input(x)
-        self.engine(x)
-        if self.training and torch.is_grad_enabled():
-            return _flat.FlatFunction.apply(x, self, *self._param_list())
-        return self.hip_forward(x, train=self.training)
-
     def hip_forward(self, x, train: bool):
         """The logits.  train: batch statistics (the running ones and num_batches_tracked advance), every map kept
         in the engine's workspace for hip_backward."""
@@ -216,19 +191,8 @@ _ADOPTED: "weakref.WeakKeyDictionary[nn.Module, ResNet]" = weakref.WeakKeyDictio
 _LEAVES = tuple(n for cv, bn, *_ in UNITS for n in (cv, bn))
 
 
-def _pair(v):
-    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-
-
 def _refuse(why: str):
     raise L.AbdError(f"not the reference's ResNet(ResidualBlock, [2, 2, 2], ...): {why}")
-
-
-def _sub(m: nn.Module, name: str):
-    try:
-        return m.get_submodule(name)
-    except AttributeError:
-        return None
 
 
 def _check_structure(m: nn.Module):
@@ -237,20 +201,15 @@ def _check_structure(m: nn.Module):
         if not isinstance(layer, nn.Sequential) or len(layer) != 2:
             _refuse(f"{name} is missing or no Sequential of two blocks")
     for cv, bn, cin, cout, stride in UNITS:
-        c, b = _sub(m, cv), _sub(m, bn)
-        if not isinstance(c, nn.Conv2d):
-            _refuse(f"{cv} is missing or no Conv2d")
-        if ((c.in_channels, c.out_channels) != (cin, cout) or _pair(c.kernel_size) != (3, 3)
-                or _pair(c.stride) != (stride, stride) or c.padding not in (1, (1, 1)) or _pair(c.dilation) != (1, 1)
-                or c.groups != 1 or c.bias is not None or c.padding_mode != "zeros"):
-            _refuse(f"{cv} is not Conv2d({cin}, {cout}, 3, stride {stride}, padding 1, no bias)")
+        _flat.check_conv3x3(m, cv, cin, cout, stride, False, _refuse)
+        b = _flat.sub(m, bn)
         if not isinstance(b, nn.BatchNorm2d):
             _refuse(f"{bn} is missing or no BatchNorm2d")
         if (b.num_features != cout or b.eps != 1e-5 or b.momentum != 0.1 or not b.affine
                 or not b.track_running_stats):
             _refuse(f"{bn} is not BatchNorm2d({cout}) with eps 1e-5, momentum 0.1, affine, running statistics")
     for name, _, _, _, ud in BLOCKS:
-        blk = _sub(m, name)
+        blk = _flat.sub(m, name)
         ds = getattr(blk, "downsample", None)
         if ud < 0:
             if ds is not None:
@@ -264,14 +223,14 @@ def _check_structure(m: nn.Module):
     c = getattr(m, "conv2d", None)
     if not isinstance(c, nn.Conv2d):
         _refuse("conv2d is missing or no Conv2d")
-    if ((c.in_channels, c.out_channels) != (64, 64) or _pair(c.kernel_size) != (1, 1) or _pair(c.stride) != (2, 1)
-            or _pair(c.padding) != (0, 0) or _pair(c.dilation) != (1, 1) or c.groups != 1 or c.bias is None):
+    if ((c.in_channels, c.out_channels) != (64, 64) or _flat.pair(c.kernel_size) != (1, 1) or _flat.pair(c.stride) != (2, 1)
+            or _flat.pair(c.padding) != (0, 0) or _flat.pair(c.dilation) != (1, 1) or c.groups != 1 or c.bias is None):
         _refuse("conv2d is not Conv2d(64, 64, (1, 1), stride (2, 1), bias)")
     p = getattr(m, "avg_pool", None)
     if not isinstance(p, nn.AvgPool2d):
         _refuse("avg_pool is missing or no AvgPool2d")
     stride = p.stride if p.stride is not None else p.kernel_size
-    if (_pair(p.kernel_size) != (4, 4) or _pair(stride) != (4, 4) or _pair(p.padding) != (0, 0) or p.ceil_mode
+    if (_flat.pair(p.kernel_size) != (4, 4) or _flat.pair(stride) != (4, 4) or _flat.pair(p.padding) != (0, 0) or p.ceil_mode
             or not p.count_include_pad or p.divisor_override is not None):
         _refuse("avg_pool is not AvgPool2d(4)")
     f = getattr(m, "fc", None)
@@ -300,25 +259,19 @@ def adopt(module: nn.Module) -> ResNet:
     still works.  One adoption per instance (a weak cache; the instance itself is not touched)."""
     if isinstance(module, ResNet):
         return module
-    if not isinstance(module, nn.Module) or type(module).__name__ != "ResNet":
+    if not adoptable(module):
         _refuse(f"got {type(module).__name__}")
-    got = _ADOPTED.get(module)
-    if got is not None and all(getattr(got, n) is getattr(module, n, None) for n in CHILDREN) and all(
-            leaf is _sub(module, n) for leaf, n in zip(got._leaves, _LEAVES)):
-        return got
-    _check_structure(module)
-    new = ResNet.__new__(ResNet)
-    nn.Module.__init__(new)
-    new.in_channels = 64
-    for name in CHILDREN:
-        new.add_module(name, getattr(module, name))
-    new._init_abd()
-    new._leaves = tuple(_sub(module, n) for n in _LEAVES)   # what the cache compares: a layer replaced inside a
-    new.train(module.training)                              # shared Sequential shows here only
-    _ADOPTED[module] = new
+    new = _flat.adopt_into(
+        ResNet, module, CHILDREN, _ADOPTED, _check_structure,
+        lambda got, m: all(getattr(got, n) is getattr(m, n, None) for n in CHILDREN) and all(
+            leaf is _flat.sub(m, n) for leaf, n in zip(got._leaves, _LEAVES)))
+    if not hasattr(new, "_leaves"):   # a fresh adoption; a cached one is returned as it is
+        new.in_channels = 64
+        # what the cache compares: a layer replaced inside a shared Sequential shows here only
+        new._leaves = tuple(_flat.sub(module, n) for n in _LEAVES)
     return new
 
 
 def adoptable(module) -> bool:
     """A module ``adopt`` would look at: named ResNet, but not this package's class."""
-    return isinstance(module, nn.Module) and not isinstance(module, ResNet) and type(module).__name__ == "ResNet"
+    return _flat.adoptable(module, ResNet)

@@ -56,6 +56,7 @@ class _Engine(_flat.FlatEngine):
 class RNN(_flat.FlatModule, nn.Module):
     """Reference-compatible RNN whose forward/backward run on libabd (HIP)."""
 
+    NAME = "RNN"
     PARAM_ORDER, ARGS, ENGINE = PARAM_ORDER, L.RnnArgs, _Engine
     BACKWARD_ORDER = ("RNN backward must directly follow its forward (activations live in the shared workspace, and "
                       "backward consumes them)")
@@ -71,26 +72,12 @@ class RNN(_flat.FlatModule, nn.Module):
         self.gemm_precision = "f32"
 
     # ------------------------------------------------------------------ settings
-    def set_gemm_precision(self, precision: str):
-        """fp32 products only ('f32', or 'f32split' which names the same accuracy class): 'bf16' raises
-        AbdError."""
-        if precision not in L.PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(L.PRECISIONS)}, got {precision!r}")
-        if precision == "bf16":
-            raise L.AbdError("RNN has no bf16 mode: every product is fp32 (DESIGN.md §5)")
-        return self
-
     def __setstate__(self, state):
         # also the target of reference-format checkpoints (training.reference_pickle_object)
         super().__setstate__(state)
         for k, v in (("_engine", None), ("gemm_precision", "f32"), ("hidden_size", HIDDEN), ("num_layers", LAYERS)):
             if k not in self.__dict__:
                 self.__dict__[k] = v
-
-    def __getstate__(self):
-        st = self.__dict__.copy()
-        st["_engine"] = None
-        return st
 
     # ------------------------------------------------------------------ binding
     def engine(self, x: torch.Tensor) -> _Engine:

@@ -77,7 +77,7 @@ def param_shapes(lf, K):
 
 
 def plan_slices(rows, max_slices=MAX_SLICES, min_rows=SLICE_ROWS, k_step=32):
-    """lstm_common.inc's plan_slices: (slices, rows per slice) of a reduction over `rows` rows."""
+    """net_common.inc's plan_slices: (slices, rows per slice) of a reduction over `rows` rows."""
     ksplit = max(1, min(max_slices, rows // min_rows))
     kchunk = -(-rows // ksplit)
     kchunk = -(-kchunk // k_step) * k_step

@@ -50,7 +50,7 @@ def half(n):
 
 
 def plan_slices(rows, max_slices=MAX_SLICES, min_rows=SLICE_ROWS, k_step=K_STEP):
-    """lstm_common.inc's plan_slices: (slices, rows per slice) of a reduction over `rows` rows."""
+    """net_common.inc's plan_slices: (slices, rows per slice) of a reduction over `rows` rows."""
     ksplit = max(1, min(max_slices, rows // min_rows))
     kchunk = -(-rows // ksplit)
     kchunk = -(-kchunk // k_step) * k_step
