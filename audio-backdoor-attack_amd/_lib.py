@@ -55,6 +55,10 @@ EXPORTS = (
     "abd_resnet_running_count", "abd_resnet_running_offsets", "abd_resnet_tile_info", "abd_resnet_linear_features",
     "abd_resnet_workspace_bytes", "abd_resnet_workspace_offset", "abd_resnet_forward", "abd_resnet_backward",
     "abd_resnet_train_step", "abd_resnet_eval",
+    "abd_smalllstm_create", "abd_smalllstm_destroy", "abd_smalllstm_param_count", "abd_smalllstm_param_offsets",
+    "abd_smalllstm_running_count", "abd_smalllstm_running_offsets", "abd_smalllstm_tile_info",
+    "abd_smalllstm_rnn_features", "abd_smalllstm_workspace_bytes", "abd_smalllstm_workspace_offset",
+    "abd_smalllstm_forward", "abd_smalllstm_backward", "abd_smalllstm_train_step", "abd_smalllstm_eval",
     "abd_profile_start", "abd_profile_start_every", "abd_profile_step", "abd_profile_stop",
 )
 
@@ -161,6 +165,11 @@ class ResNetArgs(C.Structure):
         ("logits_out", C.c_void_p), ("metrics", C.c_void_p), ("grad_scale", C.c_float),
         ("num_batches_tracked", C.c_void_p),
     ]
+
+
+class SmallLstmArgs(C.Structure):
+    """abd_smalllstm_args: the fields of abd_lstmattn_args (one dropout mask, the running statistics)."""
+    _fields_ = list(LstmAttnArgs._fields_)
 
 
 class FinetuneRegArgs(C.Structure):
@@ -358,6 +367,20 @@ def _declare(lib):
         "abd_resnet_backward": (i32, [vp, C.POINTER(ResNetArgs), vp, vp, sz, vp]),
         "abd_resnet_train_step": (i32, [vp, C.POINTER(ResNetArgs), vp, sz, vp]),
         "abd_resnet_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "abd_smalllstm_create": (i32, [i32, i32, i32, C.POINTER(vp)]),
+        "abd_smalllstm_destroy": (None, [vp]),
+        "abd_smalllstm_param_count": (i64, [vp]),
+        "abd_smalllstm_param_offsets": (i32, [vp, C.POINTER(i64)]),
+        "abd_smalllstm_running_count": (i64, [vp]),
+        "abd_smalllstm_running_offsets": (i32, [vp, C.POINTER(i64)]),
+        "abd_smalllstm_tile_info": (i32, [i32]),
+        "abd_smalllstm_rnn_features": (i64, [i32, i32]),
+        "abd_smalllstm_workspace_bytes": (sz, [vp, i64]),
+        "abd_smalllstm_workspace_offset": (i64, [vp, i64, C.c_char_p]),
+        "abd_smalllstm_forward": (i32, [vp, C.POINTER(SmallLstmArgs), i32, vp, sz, vp]),
+        "abd_smalllstm_backward": (i32, [vp, C.POINTER(SmallLstmArgs), vp, vp, sz, vp]),
+        "abd_smalllstm_train_step": (i32, [vp, C.POINTER(SmallLstmArgs), vp, sz, vp]),
+        "abd_smalllstm_eval": (i32, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "abd_profile_start": (i32, [C.c_ulonglong, i32]),
         "abd_profile_start_every": (i32, [C.c_ulonglong, i32, i32]),
         "abd_profile_step": (i32, []),

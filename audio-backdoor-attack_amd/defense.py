@@ -98,13 +98,15 @@ def combine(loss_sums, sizes, correct, n: int):
 
 def _refuse_lstm(model, what="the defences"):
     """The defences are smallcnn's (conv1..conv3 / bn1..bn3 / fc1 / fc2 and the abd_smallcnn_* entry points):
-    lstmwithattention, RNN, largecnn and ResNet (reference-built instances included), whose engines look alike but whose
-    flat buffers are laid out differently, are refused; every other module is treated as before."""
+    lstmwithattention, RNN, largecnn, ResNet and smalllstm (reference-built instances included), whose engines look alike
+    but whose flat buffers are laid out differently, are refused; every other module is treated as before."""
     from .models_lstm import lstmwithattention
     from .models_rnn import RNN
     from .models_largecnn import largecnn, adoptable
     from .models_resnet import ResNet, adoptable as resnet_adoptable
-    if isinstance(model, (lstmwithattention, RNN, largecnn, ResNet)) or adoptable(model) or resnet_adoptable(model):
+    from .models_smalllstm import smalllstm, adoptable as smalllstm_adoptable
+    if (isinstance(model, (lstmwithattention, RNN, largecnn, ResNet, smalllstm)) or adoptable(model)
+            or resnet_adoptable(model) or smalllstm_adoptable(model)):
         raise L.AbdError(f"{what} run the abd_amd smallcnn only, got {type(model).__name__} (DESIGN.md §5)")
 
 

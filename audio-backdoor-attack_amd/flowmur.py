@@ -35,7 +35,8 @@ def _as_abd_smallcnn(model):
     if isinstance(model, smallcnn):
         return model
     sd = model.state_dict()
-    if "fc1.weight" not in sd or "conv1.weight" not in sd or type(model).__name__ == "largecnn":
+    if ("fc1.weight" not in sd or "conv1.weight" not in sd or "rnn.weight_ih_l0" in sd
+            or type(model).__name__ in ("largecnn", "smalllstm")):
         raise L.AbdError(f"FlowMur trigger optimisation accelerates the smallcnn benign model only, got "
                          f"{type(model).__name__}")
     m = smallcnn(sd["fc2.weight"].shape[0], sd["fc1.weight"].shape[1])

@@ -708,12 +708,12 @@ def _(x, labels, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracke
     return x.new_empty((x.shape[0], num_classes))
 
 
-# --------------------------------------------------------------------------- lstmwithattention, RNN, largecnn, ResNet
+# --------------------------------------------------------------------------- lstmwithattention, RNN, largecnn, ResNet, smalllstm
 _FLAT_NETS: dict = {}
 
 
 def _flat_net(prefix: str, T: int, F: int, K: int):
-    """A cached libabd handle (prefix abd_lstmattn / abd_rnn / abd_largecnn / abd_resnet) for one geometry: shapes only,
+    """A cached libabd handle (prefix abd_lstmattn / abd_rnn / abd_largecnn / abd_resnet / abd_smalllstm) for one geometry: shapes only,
     no device state."""
     key = (prefix, int(T), int(F), int(K))
     h = _FLAT_NETS.get(key)
@@ -949,4 +949,57 @@ def resnet_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor], p
 @resnet_train_step.register_fake
 def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics, num_classes,
       adam_step, lr, beta1, beta2, eps):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+def _smalllstm_eval(x, params, running, num_classes, labels, indicators, metrics):
+    return _flat_eval("abd_smalllstm", "smalllstm", x, params, (running,), num_classes, labels, indicators, metrics)
+
+
+@torch.library.custom_op("abd::smalllstm_eval", mutates_args=())
+def smalllstm_eval(x: Tensor, params: Tensor, running: Tensor, num_classes: int) -> Tensor:
+    """model.eval() forward of smalllstm: (B, 1, H, W) -> log-probabilities (B, K); running BN statistics, no
+    dropout, nothing updated."""
+    return _smalllstm_eval(x, params, running, num_classes, None, None, None)
+
+
+@smalllstm_eval.register_fake
+def _(x, params, running, num_classes):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::smalllstm_eval_metrics", mutates_args=("metrics",))
+def smalllstm_eval_metrics(x: Tensor, params: Tensor, running: Tensor, num_classes: int, labels: Tensor,
+                           indicators: Optional[Tensor], metrics: Tensor) -> Tensor:
+    """The eval forward plus test()'s loss / accuracy / ASR counters accumulated into metrics (int64[8]);
+    returns the log-probabilities."""
+    return _smalllstm_eval(x, params, running, num_classes, labels, indicators, metrics)
+
+
+@smalllstm_eval_metrics.register_fake
+def _(x, params, running, num_classes, labels, indicators, metrics):
+    return x.new_empty((x.shape[0], num_classes))
+
+
+@torch.library.custom_op("abd::smalllstm_train_step",
+                         mutates_args=("params", "grads", "exp_avg", "exp_avg_sq", "running", "num_batches_tracked",
+                                       "metrics"))
+def smalllstm_train_step(x: Tensor, labels: Tensor, indicators: Optional[Tensor], params: Tensor, grads: Tensor,
+                         exp_avg: Tensor, exp_avg_sq: Tensor, running: Tensor, num_batches_tracked: Tensor,
+                         metrics: Tensor, num_classes: int, adam_step: int, lr: float, beta1: float, beta2: float,
+                         eps: float, seed: int, counter: int, mask: Optional[Tensor] = None) -> Tensor:
+    """One fused train() iteration of smalllstm on the device; returns the batch's log-probabilities (B, K).
+    adam_step >= 1 applies torch.optim.Adam (that step index); 0 leaves params untouched.  mask: a (B, 32, T, Wf)
+    uint8 keep mask of drop1 in place of the device hash."""
+    a = L.SmallLstmArgs()
+    a.running, a.num_batches_tracked = running.data_ptr(), num_batches_tracked.data_ptr()
+    a.seed, a.counter = int(seed), int(counter)
+    a.mask_in = _ptr(mask)
+    return _flat_train_step("abd_smalllstm", "smalllstm", a, x, labels, indicators, params, grads, exp_avg,
+                            exp_avg_sq, metrics, num_classes, adam_step, lr, beta1, beta2, eps)
+
+
+@smalllstm_train_step.register_fake
+def _(x, labels, indicators, params, grads, exp_avg, exp_avg_sq, running, num_batches_tracked, metrics, num_classes,
+      adam_step, lr, beta1, beta2, eps, seed, counter, mask=None):
     return x.new_empty((x.shape[0], num_classes))

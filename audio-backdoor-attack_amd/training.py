@@ -25,27 +25,32 @@ from .models_rnn import RNN
 from .models_largecnn import largecnn, adopt, adoptable
 from . import models_resnet
 from .models_resnet import ResNet
+from . import models_smalllstm
+from .models_smalllstm import smalllstm
 from .resident import resident_batches
 
 # the models whose train() / test() steps run on libabd
-ACCELERATED = (smallcnn, lstmwithattention, RNN, largecnn, ResNet)
+ACCELERATED = (smallcnn, lstmwithattention, RNN, largecnn, ResNet, smalllstm)
 
 
 def accelerated(model):
-    """The model train() / test() drive: model itself, or, for a reference-built ``utils.models.largecnn`` or
-    ``utils.models.ResNet`` instance (what the unmodified attack scripts hold), its adoption (models_largecnn.adopt /
-    models_resnet.adopt: the same submodules, Parameter objects and BatchNorm buffers under the abd class).  A module
-    named largecnn or ResNet of another structure raises AbdError."""
+    """The model train() / test() drive: model itself, or, for a reference-built ``utils.models.largecnn``,
+    ``utils.models.ResNet`` or ``utils.models.smalllstm`` instance (what the unmodified attack scripts hold), its
+    adoption (models_largecnn.adopt / models_resnet.adopt / models_smalllstm.adopt: the same submodules, Parameter
+    objects and BatchNorm buffers under the abd class).  A module named largecnn, ResNet or smalllstm of another
+    structure raises AbdError."""
     if adoptable(model):
         return adopt(model)
+    if models_smalllstm.adoptable(model):
+        return models_smalllstm.adopt(model)
     return models_resnet.adopt(model) if models_resnet.adoptable(model) else model
 
 
 def require_smallcnn(model, what: str):
     """Raise AbdError unless model is the abd_amd smallcnn: the data-parallel / SyncBN trainer, the direct
     smallcnn step and the defences drive the abd_smallcnn_* entry points, whose handle and flat buffer layout
-    are smallcnn's own (lstmwithattention, RNN, largecnn and ResNet -- adopted reference instances included -- have the
-    same Python surface but another layout)."""
+    are smallcnn's own (lstmwithattention, RNN, largecnn, ResNet and smalllstm -- adopted reference instances included --
+    have the same Python surface but another layout)."""
     if not isinstance(model, smallcnn):
         raise L.AbdError(f"{what} runs the abd_amd smallcnn only, got {type(model).__name__}")
 
@@ -310,13 +315,42 @@ def resnet_train_step(model: ResNet, x, labels, indicators, adam: AdamBinding | 
     return _flat_step(eng, a, x)
 
 
+def smalllstm_train_step(model: smalllstm, x, labels, indicators, adam: AdamBinding | None,
+                         metrics: torch.Tensor | None, mask=None, mask_out=None, do_update=True, grad_scale=1.0,
+                         seed=None, logits_out=None):
+    """One fused device step of smalllstm (forward + CE on the log-probabilities + backward [+ Adam]) through the
+    C ABI; the running statistics and num_batches_tracked advance.  mask: a (B, 32, T, Wf) uint8 keep mask of drop1
+    in place of the device hash; mask_out receives the mask used."""
+    model._check_input(x)
+    x = x.contiguous()
+    eng, a = _flat_step_args(model, x, labels, indicators, adam, metrics, do_update, grad_scale, logits_out)
+    eng.last_train_token = -1   # the step overwrites the workspace a pending autograd backward would read
+    a.seed = dropout_seed(x.device, model) if seed is None else seed
+    a.counter = model._step
+    model._step += 1
+    if mask is not None:
+        a.mask_in = mask.data_ptr()
+    if mask_out is not None:
+        a.mask_out = mask_out.data_ptr()
+    return _flat_step(eng, a, x)
+
+
 def op_train_step(model: smallcnn | lstmwithattention, x, labels, indicators, adam: AdamBinding,
                   metrics: torch.Tensor):
     """train()'s per-batch step through the model's custom op, ``abd::smallcnn_train_step``,
-    ``abd::lstmattn_train_step``, ``abd::rnn_train_step``, ``abd::largecnn_train_step`` or
-    ``abd::resnet_train_step`` (ops.py)."""
+    ``abd::lstmattn_train_step``, ``abd::rnn_train_step``, ``abd::largecnn_train_step``,
+    ``abd::resnet_train_step`` or ``abd::smalllstm_train_step`` (ops.py)."""
     from . import ops  # noqa: F401  (registers torch.ops.abd)
     eng = model.engine(x)
+    if isinstance(model, smalllstm):
+        adam.step += 1
+        torch.ops.abd.smalllstm_train_step(
+            x, labels, indicators, eng.params, eng.grads, eng.exp_avg, eng.exp_avg_sq, eng.running, eng.nbt, metrics,
+            eng.K, adam.step, adam.lr, adam.betas[0], adam.betas[1], adam.eps, dropout_seed(x.device, model),
+            model._step, None)
+        model._step += 1
+        eng.last_train_token = -1
+        return
     if isinstance(model, ResNet):
         adam.step += 1
         torch.ops.abd.resnet_train_step(
@@ -380,8 +414,8 @@ def read_metrics(m: torch.Tensor):
 
 
 def _unsupported(model):
-    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn / lstmwithattention / RNN / largecnn / ResNet + Adam + "
-                     f"CrossEntropyLoss hot path only; got {type(model).__name__} (other models and optimizers are out "
+    raise L.AbdError(f"abd_amd accelerates the reference's smallcnn / lstmwithattention / RNN / largecnn / ResNet / smalllstm + "
+                     f"Adam + CrossEntropyLoss hot path only; got {type(model).__name__} (other models and optimizers are out "
                      f"of scope, see DESIGN.md)")
 
 
@@ -422,6 +456,8 @@ def _eval_batches(model, loader, dev, dict_items):
             torch.ops.abd.largecnn_eval_metrics(x, eng.params, eng.K, y, ind, metrics)
         elif isinstance(model, ResNet):
             torch.ops.abd.resnet_eval_metrics(x, eng.params, eng.running, eng.K, y, ind, metrics)
+        elif isinstance(model, smalllstm):
+            torch.ops.abd.smalllstm_eval_metrics(x, eng.params, eng.running, eng.K, y, ind, metrics)
         elif isinstance(model, lstmwithattention):
             torch.ops.abd.lstmattn_eval_metrics(x, eng.params, eng.running, eng.K, y, ind, metrics)
         else:
@@ -555,7 +591,7 @@ def reference_pickle_object(model: smallcnn | lstmwithattention, module: str = "
 
 
 def save_reference_checkpoint(model, path):
-    """torch.save in the reference's format: abd smallcnn / lstmwithattention / RNN / largecnn -> a pickle of the
+    """torch.save in the reference's format: abd smallcnn / lstmwithattention / RNN / largecnn / smalllstm -> a pickle of the
     utils.models class of the same name; any other module is saved as is (the reference's behaviour)."""
     if isinstance(model, smallcnn):
         torch.save(reference_pickle_object(model), path, pickle_module=_GlobalPickleModule())
@@ -566,6 +602,8 @@ def save_reference_checkpoint(model, path):
         torch.save(reference_pickle_object(model, name="RNN"), path, pickle_module=_GlobalPickleModule())
     elif isinstance(model, largecnn):
         torch.save(reference_pickle_object(model, name="largecnn"), path, pickle_module=_GlobalPickleModule())
+    elif isinstance(model, smalllstm):
+        torch.save(reference_pickle_object(model, name="smalllstm"), path, pickle_module=_GlobalPickleModule())
     else:
         torch.save(model, path)
 

@@ -1080,6 +1080,103 @@ int abd_resnet_eval(abd_resnet* net, const float* x, int64_t batch, const float*
                     const int64_t* labels, const int64_t* indicators, float* logits, int64_t* metrics,
                     void* workspace, size_t workspace_bytes, abd_stream_t stream);
 
+/* ------------------------------------------------------------------ smalllstm
+ * Replaces utils/models.py:121-178 smalllstm(num_classes, rnn_features): conv1 2x2 (1->64, bias) relu bn1
+ * MaxPool2d((1,3)); conv2 2x2 (64->64) relu bn2 MaxPool2d((2,2), padding (1,1)); conv3 2x2 (64->32) relu bn3
+ * MaxPool2d((2,2), padding (0,1)); Dropout(0.4); the pooled (B, 32, T, Wf) map permuted to (B, T, Wf * 32) feeds
+ * nn.LSTM(32 Wf, 128, 2, batch_first) from a zero state; fc2 (128 -> K) on the top layer's last step;
+ * log_softmax.  ReLU comes before BatchNorm.  Input (B, 1, H, W) fp32; log-probabilities out; the loss is cross
+ * entropy on them.  Geometry (integer division): H1 = H - 1, W1 = W - 1, Wp1 = W1 / 3, H2 = H1 - 1,
+ * W2 = Wp1 - 1, Hp2 = H2 / 2 + 1, Wp2 = W2 / 2 + 1, H3 = Hp2 - 1, W3 = Wp2 - 1, T = (H3 - 2) / 2 + 1,
+ * Wf = W3 / 2 + 1.
+ *
+ * Parameters live in ONE flat fp32 buffer in named_parameters() order, 24 tensors: conv1.weight, conv1.bias,
+ * bn1.weight, bn1.bias, the same for conv2 / bn2 and conv3 / bn3, rnn.weight_ih_l0, weight_hh_l0, bias_ih_l0,
+ * bias_hh_l0, the same for l1, fc1.weight (128, 224), fc1.bias, fc2.weight, fc2.bias.  fc1 is a parameter the
+ * forward never reads: its gradient is written as exactly zero.  running: bn1, bn2, bn3 running_mean then
+ * running_var, 320 floats; num_batches_tracked: int64[3].
+ *
+ * Every product is fp32.  Activations are channels-last in the workspace, so the pooled map IS the LSTM's input
+ * sequence.  conv2 and conv3 and their gradients are implicit GEMMs on v_mfma_f32_16x16x4_f32; BatchNorm sums are
+ * per-block double partials combined in block order; the max pools take torch's first maximum and backward
+ * recomputes it.  Each LSTM layer's recurrence is ONE launch for all T steps (one more for its BPTT): a workgroup
+ * owns 16 batch rows and keeps W_hh in registers as MFMA operands.  There are no float atomics and two calls on
+ * equal inputs give bit-equal results.  The entry points allocate nothing, never synchronise and take nothing
+ * from host memory but their arguments. */
+typedef struct abd_smalllstm abd_smalllstm;
+
+/* the fields of abd_lstmattn_args */
+typedef struct abd_smalllstm_args {
+  const float* x;            /* (B,1,H,W)                                      */
+  const int64_t* labels;     /* (B)                                            */
+  const int64_t* indicators; /* (B) poison indicator, NULL = none              */
+  int64_t batch;
+  float* params;             /* flat                                           */
+  float* grads;              /* flat (written)                                 */
+  float* exp_avg;            /* flat Adam m                                    */
+  float* exp_avg_sq;         /* flat Adam v                                    */
+  float* running;            /* 320 floats; NULL in a train-mode call leaves
+                              * the running statistics and
+                              * num_batches_tracked alone                      */
+  int64_t adam_step;         /* step index after increment (1-based)           */
+  float lr, beta1, beta2, eps;
+  int do_update;             /* 0: forward/backward only (grads), 1: + Adam    */
+  const uint8_t* mask_in;    /* optional drop1 keep mask in the reference's
+                              * (B,32,T,Wf) element order, scale 1/0.6; NULL ->
+                              * hashed from (seed, counter, global element)    */
+  uint64_t seed, counter;
+  uint8_t* mask_out;         /* optional: the mask used                        */
+  float* logits_out;         /* optional (B,K): the log-probabilities          */
+  int64_t* metrics;          /* optional ABD_METRICS_WORDS accumulators        */
+  float grad_scale;          /* multiplies the loss gradient and weights
+                              * metrics[0]'s batch-mean loss                   */
+  int64_t* num_batches_tracked; /* optional int64[3], += 1 per train forward   */
+  int64_t row_offset;        /* global batch row of row 0 (dropout hash)       */
+} abd_smalllstm_args;
+
+/* the LSTM's input width 32 * Wf for an (H, W) input; -1 below 6 x 10 (conv3 or pool3 has no window) */
+int64_t abd_smalllstm_rnn_features(int H, int W);
+/* ABD_E_UNSUPPORTED for H < 6 or W < 10, a side above 4096, a geometry whose element indices leave 32 bits,
+ * num_classes outside [1, 4096] */
+int abd_smalllstm_create(int H, int W, int num_classes, abd_smalllstm** net);
+void abd_smalllstm_destroy(abd_smalllstm* net);
+int64_t abd_smalllstm_param_count(const abd_smalllstm* net);
+int abd_smalllstm_param_offsets(const abd_smalllstm* net, int64_t* offsets /* 25 */);
+int64_t abd_smalllstm_running_count(const abd_smalllstm* net);
+/* offsets[i]: bn<i+1>'s running_mean inside running (its running_var follows); offsets[3] = the count */
+int abd_smalllstm_running_offsets(const abd_smalllstm* net, int64_t* offsets /* 4 */);
+/* kernel geometry (tests): 0 rows of a conv block tile, 1 the convs' K-step, 2 least rows of a weight-gradient
+ * slice, 3 most slices of a conv weight gradient, 4 least pixels of a BatchNorm partial block, 5 most such
+ * blocks, 6 batch rows of a recurrent workgroup, 7 / 8 edge of the small / large GEMM block tile, 9 the GEMM's
+ * K-step, 10 most slices of an LSTM weight gradient, 11 rows above which column sums take two stages, 12 least
+ * count of large GEMM tiles for which the large tile is used; -1 otherwise */
+int abd_smalllstm_tile_info(int what);
+size_t abd_smalllstm_workspace_bytes(const abd_smalllstm* net, int64_t batch);
+/* Byte offset of a saved map inside the workspace (tests), -1 for an unknown name.  For i = 1..3: z<i> conv i's
+ * output after bias and ReLU (what BatchNorm reads), a<i> the BatchNorm output, p<i> the pooled map, all
+ * channels-last; s<i> the batch mean[C] then 1 / sqrt(var + eps)[C].  seq ((B, T, Wf, 32): the LSTM input, p3
+ * after dropout), keep (uint8, the reference's (B, 32, T, Wf) order).  For layer l = 0, 1: h<l> c<l> ((B, T, 128)),
+ * g<l> ((B, T, 512): the activated gates i f g o after a forward, the gate gradients after a backward).  logits
+ * (the log-probabilities), dlogits, rowinfo. */
+int64_t abd_smalllstm_workspace_offset(const abd_smalllstm* net, int64_t batch, const char* name);
+/* forward keeps every map in the workspace and writes the log-probabilities to a->logits_out (if set);
+ * train_mode selects batch statistics (running statistics and num_batches_tracked updated when given) and
+ * dropout vs the running statistics (required then).  backward consumes d(log-probabilities), overwrites the
+ * saved gates, and must follow a train-mode forward on the same workspace. */
+int abd_smalllstm_forward(abd_smalllstm* net, const abd_smalllstm_args* a, int train_mode, void* workspace,
+                          size_t workspace_bytes, abd_stream_t stream);
+int abd_smalllstm_backward(abd_smalllstm* net, const abd_smalllstm_args* a, const float* dlogits, void* workspace,
+                           size_t workspace_bytes, abd_stream_t stream);
+/* forward, cross entropy on the log-probabilities (mean over the batch) with the ABD_METRICS_WORDS counters,
+ * backward, and abd_adam_f32 on the flat buffer when do_update.  labels are required (ABD_E_INVALID). */
+int abd_smalllstm_train_step(abd_smalllstm* net, const abd_smalllstm_args* a, void* workspace, size_t workspace_bytes,
+                             abd_stream_t stream);
+/* eval forward: running statistics, no dropout, nothing updated.  Writes the log-probabilities and, if
+ * labels != NULL, accumulates the counters like test(). */
+int abd_smalllstm_eval(abd_smalllstm* net, const float* x, int64_t batch, const float* params, const float* running,
+                       const int64_t* labels, const int64_t* indicators, float* logits, int64_t* metrics,
+                       void* workspace, size_t workspace_bytes, abd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
