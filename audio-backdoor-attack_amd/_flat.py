@@ -1,5 +1,5 @@
-"""The flat-buffer engine shared by ``models_lstm.lstmwithattention``, ``models_rnn.RNN``, ``models_largecnn.largecnn``
-and ``models_resnet.ResNet``.
+"""The flat-buffer engine shared by ``models_lstm.lstmwithattention``, ``models_rnn.RNN``, ``models_largecnn.largecnn``,
+``models_resnet.ResNet`` and ``models_smalllstm.smalllstm``.
 
 Both models keep their parameters in ONE flat device buffer in ``PARAM_ORDER`` (and their BatchNorm running
 statistics, if any, in a second one), drive a family of C entry points that differ only in their prefix
@@ -15,6 +15,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .models import draw_dropout_nonce
+
+# STATE of a model with device dropout: the step counter and the nonce of its mask stream
+DROPOUT_STATE = (("_engine", None), ("_step", 0), ("_dropout_nonce", None), ("gemm_precision", "f32"))
 
 
 def net_handle(prefix: str, T: int, F: int, K: int):
@@ -81,6 +85,18 @@ class FlatModule:
     BACKWARD_CONSUMES = False
     NAME = "model"    # the display name in messages
     TRANSIENT = ()    # attributes that live for one launch and are not pickled
+    STATE = (("_engine", None), ("gemm_precision", "f32"))   # the instance attributes and what they start as
+
+    def _init_abd(self):
+        for k, v in self.STATE:
+            setattr(self, k, v)
+
+    def __setstate__(self, state):
+        # also the target of reference-format checkpoints (training.reference_pickle_object)
+        super().__setstate__(state)
+        for k, v in self.STATE:
+            if k not in self.__dict__:
+                self.__dict__[k] = v
 
     def set_gemm_precision(self, precision: str):
         """fp32 products only ('f32', or 'f32split' which names the same accuracy class): 'bf16' raises
@@ -157,6 +173,15 @@ class FlatModule:
                 rnn._flat_weights = [getattr(rnn, n) for n in rnn._flat_weights_names]
         self._engine = new
         return new
+
+    def _bind_dropout(self, T: int, F: int, device):
+        """_bind for a model with device dropout: a model that has no nonce yet draws it when the engine was
+        re-bound."""
+        bound = self._engine
+        eng = self._bind(T, F, device)
+        if eng is not bound and getattr(self, "_dropout_nonce", None) is None:
+            self._dropout_nonce = draw_dropout_nonce(device)
+        return eng
 
     def _args(self, eng, x, B):
         a = self.ARGS()

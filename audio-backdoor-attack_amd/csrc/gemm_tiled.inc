@@ -1,6 +1,7 @@
-// The tile geometry and the choice of tile that rnn.hip's gemm_tiled_kernel and largecnn.hip's conv_gemm_kernel
-// share; included after the file's kT.  Each keeps its own text of the tile loop: one shared body with the loaders
-// as a compile-time policy compiled to a schedule 0.4 to 1.9 % slower per largecnn step (profiles/conv_core/equal.md).
+// The tile geometry and the choice of tile that gemm_tiled_kernel (gemm_tiled_kernel.inc: rnn.hip, smalllstm.hip) and
+// largecnn.hip's conv_gemm_kernel share; included after the file's kT.  Those are the two texts of the tile loop:
+// one shared body with the loaders as a compile-time policy compiled to a schedule 0.4 to 1.9 % slower per largecnn
+// step (profiles/conv_core/equal.md).
 
 constexpr int kBK = 32;            // K-step of the tiled kernels
 constexpr int kSmallTile = 64, kLargeTile = 128;

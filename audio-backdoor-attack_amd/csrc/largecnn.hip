@@ -53,17 +53,7 @@ enum { P_C1W, P_C1B, P_C2W, P_C2B, P_C3W, P_C3B, P_C4W, P_C4B, P_C5W, P_C5B, P_F
 // GemmArgs and its three forms, the host helpers; colsum_kernel, ce_kernel, metrics_kernel
 #include "net_common.inc"
 #include "gemm_tiled.inc"   // kBK, the tile sizes, f16v and launch_tiled
-
-// the dropout hash of the smallcnn kernels: keep with probability 1 - p
-__device__ __forceinline__ bool keep_hash(uint64_t seed, uint64_t stream, uint64_t idx, float p) {
-  uint64_t z = seed ^ (stream * 0x9E3779B97F4A7C15ull) ^ (idx * 0xD1B54A32D192ED03ull);
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-  return u >= p;
-}
+#include "log_softmax.inc"  // lsm_fwd_kernel, lsm_bwd_kernel
 
 // ------------------------------------------------------------------ LDS-tiled fp32 MFMA GEMM with a pixel gather
 // mode 0: the plain GEMM of GemmArgs.
@@ -376,30 +366,6 @@ __global__ void __launch_bounds__(kT) act_bwd_kernel(float* dh, const float* h, 
   const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
   if (e >= total) return;
   dh[e] = h[e] > 0.0f ? dh[e] * 2.0f : 0.0f;
-}
-
-// one wave per row: lp = z - max - log(sum exp(z - max))
-__global__ void __launch_bounds__(64) lsm_fwd_kernel(const float* z, float* lp, int K) {
-  const int row = blockIdx.x, lane = threadIdx.x;
-  const float* zr = z + (int64_t)row * K;
-  float mx = -INFINITY;
-  for (int j = lane; j < K; j += 64) mx = fmaxf(mx, zr[j]);
-  mx = abd::wave_max(mx);
-  float se = 0.0f;
-  for (int j = lane; j < K; j += 64) se += expf(zr[j] - mx);
-  se = abd::wave_sum(se);
-  const float lse = __ocml_log_f32(se);
-  for (int j = lane; j < K; j += 64) lp[(int64_t)row * K + j] = (zr[j] - mx) - lse;
-}
-
-// dz = dlp - exp(lp) * sum(dlp)
-__global__ void __launch_bounds__(64) lsm_bwd_kernel(const float* lp, const float* dlp, float* dz, int K) {
-  const int row = blockIdx.x, lane = threadIdx.x;
-  const int64_t o = (int64_t)row * K;
-  float s = 0.0f;
-  for (int j = lane; j < K; j += 64) s += dlp[o + j];
-  s = abd::wave_sum(s);
-  for (int j = lane; j < K; j += 64) dz[o + j] = dlp[o + j] - expf(lp[o + j]) * s;
 }
 
 // conv1's weight gradient: block i takes pooled pixels [i * chunk, (i + 1) * chunk); thread (lane, channel) walks

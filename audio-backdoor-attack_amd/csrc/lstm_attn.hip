@@ -50,20 +50,9 @@ struct Offs {
   __host__ __device__ int64_t operator[](int i) const { return v[i]; }
 };
 
-// shared with rnn.hip: backward cell, GemmArgs and its three forms, the host helpers; colsum_kernel,
-// ce_kernel, metrics_kernel
+// shared with rnn.hip and smalllstm.hip: backward cell, colsum; GemmArgs and its three forms, keep_hash, the host
+// helpers; colsum_kernel, ce_kernel, metrics_kernel
 #include "lstm_common.inc"
-
-// the dropout hash of the smallcnn kernels: keep with probability 1 - p
-__device__ __forceinline__ bool keep_hash(uint64_t seed, uint64_t stream, uint64_t idx, float p) {
-  uint64_t z = seed ^ (stream * 0x9E3779B97F4A7C15ull) ^ (idx * 0xD1B54A32D192ED03ull);
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-  return u >= p;
-}
 
 // ------------------------------------------------------------------ fp32 MFMA GEMM (GemmArgs)
 // One wave per 32x32 tile.
@@ -869,18 +858,13 @@ struct Ctx : CtxBase {
   }
 };
 
-int launch_gemm(hipStream_t s, GemmArgs g, int ksplit = 1) {
+int launch_gemm(hipStream_t s, GemmArgs g, int ksplit) {
   if (g.M <= 0 || g.N <= 0) return ABD_OK;
   if (ksplit <= 1) g.kchunk = (g.K + 7) & ~7;
   dim3 grid((g.M + 31) / 32, (g.N + 31) / 32, std::max(1, ksplit));
   gemm_kernel<<<grid, 64, 0, s>>>(g);
   ABD_LAUNCH_CHECK();
   return ABD_OK;
-}
-
-// out[cols] = column sums of A; two fixed-order stages past 512 rows
-int colsum(const Ctx& c, const float* A, int64_t rows, int64_t cols, int64_t ld, float* out) {
-  return launch_colsum(c, A, rows, cols, ld, out, 0, kGates, 512);
 }
 
 // Raise the kernel's dynamic-LDS limit once per device (bit d of *done = device d has it; devices past

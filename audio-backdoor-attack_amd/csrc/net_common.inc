@@ -1,7 +1,7 @@
-// What the four flat-buffer networks (lstm_attn.hip, rnn.hip, largecnn.hip, resnet.hip) share: the description
-// of a GEMM and its three forms, the host helpers around the workspace, the cross entropy and the two ends of a
-// train step.  Included inside each file's anonymous namespace, after abd_common.h (the two LSTM files include
-// it through lstm_common.inc).  Each file keeps its own GEMM kernels and launch_gemm, its Layout / make_layout,
+// What the five flat-buffer networks (lstm_attn.hip, rnn.hip, largecnn.hip, resnet.hip, smalllstm.hip) share: the
+// description of a GEMM and its three forms, the dropout hash, the host helpers around the workspace, the cross
+// entropy and the two ends of a train step.  Included inside each file's anonymous namespace, after abd_common.h (the
+// three LSTM files include it through lstm_common.inc).  Each file keeps its Layout / make_layout
 // and a Ctx derived from CtxBase with members n (the net) and L (the layout; logits, dlogits, rowinfo and colp
 // are read here).
 
@@ -50,6 +50,18 @@ GemmArgs gemm_tn(const float* D, const float* X, int64_t ldx, float* C, int M, i
   g.M = M, g.N = N, g.K = (int)rows;
   g.sam = 1, g.sak = M, g.sbk = ldx, g.sbn = 1, g.ldc = N;
   return g;
+}
+
+// ------------------------------------------------------------------ dropout hash
+// the dropout hash of the smallcnn kernels: keep with probability 1 - p
+__device__ __forceinline__ bool keep_hash(uint64_t seed, uint64_t stream, uint64_t idx, float p) {
+  uint64_t z = seed ^ (stream * 0x9E3779B97F4A7C15ull) ^ (idx * 0xD1B54A32D192ED03ull);
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
+  return u >= p;
 }
 
 // ------------------------------------------------------------------ host helpers

@@ -69,23 +69,8 @@ enum { P_C2DW = 3 * kUnits, P_C2DB, P_FCW, P_FCB, P_COUNT };
 
 // GemmArgs and its three forms, the host helpers; colsum_kernel, ce_kernel, metrics_kernel
 #include "net_common.inc"
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-// ------------------------------------------------------------------ the 16x16x4 tile product
-// As: (kBM rows) x kBK, pitch kLd; Bs: kBK x (16 TN), pitch ldb.  The wave at rows wm..wm+15 adds the K-step to
-// its TN accumulators.  Operand lanes: A[row lane & 15][k lane >> 4], B[k lane >> 4][col lane & 15].
-template <int TN>
-__device__ __forceinline__ void tile_mfma(const float* As, const float* Bs, int ldb, int wm, int lane, f4v (&acc)[TN]) {
-#pragma unroll
-  for (int kk = 0; kk < kBK / 4; ++kk) {
-    const int k = kk * 4 + (lane >> 4);
-    const float av = As[(wm + (lane & 15)) * kLd + k];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-      acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, Bs[k * ldb + j * 16 + (lane & 15)], acc[j], 0, 0, 0);
-  }
-}
+// f4v, tile_mfma, wgrad_reduce_kernel, blocks, stat_plan, the ABI entries of a net with running statistics
+#include "conv16_common.inc"
 
 // ------------------------------------------------------------------ 3x3 conv as an implicit GEMM
 // The gather: pixel (b, h, w) of the Hr x Wr index map and a tap read source pixel
@@ -201,7 +186,7 @@ __global__ void __launch_bounds__(kT) conv_kernel(ConvArgs a) {
       Bs[(e / BN) * LDB + e % BN] = br[j];
     }
     __syncthreads();
-    tile_mfma<TN>(As, Bs, LDB, wm, lane, acc);
+    tile_mfma<TN, kBK>(As, Bs, LDB, wm, lane, acc);
   }
   float* out = MODE == 1 ? a.out : a.out + (int64_t)blockIdx.z * M * BN;
 #pragma unroll
@@ -253,7 +238,7 @@ __global__ void __launch_bounds__(kT) gemm_kernel(GemmArgs a) {
       Bs[(b_kc ? e & 15 : e >> 6) * LDB + (b_kc ? e >> 4 : e & 63)] = br[i];
     }
     __syncthreads();
-    tile_mfma<4>(As, Bs, LDB, wm, lane, acc);
+    tile_mfma<4, kBK>(As, Bs, LDB, wm, lane, acc);
   }
   float* Cz = a.C + (int64_t)blockIdx.z * a.cz;
 #pragma unroll
@@ -288,17 +273,6 @@ __global__ void __launch_bounds__(kT) repack_kernel(RepackArgs a) {
   const float v = a.params[a.w[u] + e];
   a.ws[a.wf[u] + ((int64_t)tap * Cin + ci) * Cout + co] = v;
   if (a.need_wd) a.ws[a.wd[u] + ((int64_t)tap * Cout + co) * Cin + ci] = v;
-}
-
-// dw (Cout, Cin, 3, 3) = the sum over slices, in slice order, of slab (slice, tap, Cin, Cout)
-__global__ void __launch_bounds__(kT) wgrad_reduce_kernel(const float* slab, int slices, int Cout, int Cin, float* dw) {
-  const int e = blockIdx.x * kT + threadIdx.x;
-  const int per = 9 * Cout * Cin;
-  if (e >= per) return;
-  double s = 0.0;
-  for (int z = 0; z < slices; ++z) s += (double)slab[(int64_t)z * per + e];
-  const int co = e % Cout, ci = (e / Cout) % Cin, tap = e / (Cout * Cin);
-  dw[((int64_t)co * Cin + ci) * 9 + tap] = (float)s;
 }
 
 // out[n] = the sum over slices, in slice order, of slab (slice, n)
@@ -575,8 +549,6 @@ struct Ctx : CtxBase {
   float* gb(int i) const { return at<float>(L.g[i]); }
 };
 
-inline unsigned blocks(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
-
 int launch_gemm(const Ctx& c, GemmArgs g, int nz = 1) {
   if (g.M <= 0 || g.N <= 0) return ABD_OK;
   if (nz == 1) g.kchunk = std::max(g.K, 1);
@@ -631,20 +603,9 @@ int conv_wgrad(const Ctx& c, int u, const float* dy, const float* x) {
   a.C = cv.Cin, a.mul = cv.stride, a.sign = 1, a.div = 1;
   a.pixels = (int)pixels, a.kchunk = (int)sl.kchunk;
   if (int rc = launch_conv<2>(c, a, cv.Cout, 9 * cv.Cin, sl.ksplit)) return rc;
-  wgrad_reduce_kernel<<<blocks(9 * cv.Cin * cv.Cout), kT, 0, c.s>>>(a.out, sl.ksplit, cv.Cout, cv.Cin, c.g(3 * u));
+  wgrad_reduce_kernel<9><<<blocks(9 * cv.Cin * cv.Cout), kT, 0, c.s>>>(a.out, sl.ksplit, cv.Cout, cv.Cin, c.g(3 * u));
   ABD_LAUNCH_CHECK();
   return ABD_OK;
-}
-
-struct StatPlan {
-  int nb;
-  int64_t chunk;
-};
-StatPlan stat_plan(int64_t pixels) {
-  StatPlan p;
-  p.nb = (int)std::max<int64_t>(1, std::min<int64_t>(kStatBlocks, (pixels + kStatRows - 1) / kStatRows));
-  p.chunk = (pixels + p.nb - 1) / p.nb;
-  return p;
 }
 
 // a<u> = BatchNorm(z<u>) [+ res] [relu]; train: batch statistics, running statistics updated when c.running
@@ -687,7 +648,8 @@ int bn_bwd(const Ctx& c, int u, const float* g, bool masked, float* dz, float* g
   return ABD_OK;
 }
 
-int run_forward(const Ctx& c, const float* x, int train) {
+// the shared ABI entries pass the call's args struct or NULL: this forward reads nothing of it
+int run_forward(const Ctx& c, const float* x, int train, const abd_resnet_args*) {
   const abd_resnet* n = c.n;
   const int64_t B = c.B;
   RepackArgs ra{};
@@ -786,12 +748,9 @@ int run_backward(const Ctx& c, const float* x, const float* dlogits) {
   return ABD_OK;
 }
 
-int make_rctx(const abd_resnet* net, int64_t B, const float* params, float* grads, float* running, int64_t* nbt,
-              void* ws, size_t bytes, abd_stream_t stream, Ctx* c) {
-  if (int rc = make_ctx(net, B, params, grads, ws, bytes, stream, kC0, make_layout, c)) return rc;
-  c->running = running;
-  c->nbt = nbt;
-  return ABD_OK;
+int make_ctx(const abd_resnet* net, int64_t B, const float* params, float* grads, void* ws, size_t bytes,
+             abd_stream_t stream, Ctx* c) {
+  return make_ctx(net, B, params, grads, ws, bytes, stream, kC0, make_layout, c);
 }
 
 }  // namespace
@@ -888,48 +847,24 @@ int64_t abd_resnet_workspace_offset(const abd_resnet* net, int64_t batch, const 
 
 int abd_resnet_forward(abd_resnet* net, const abd_resnet_args* a, int train_mode, void* workspace,
                        size_t workspace_bytes, abd_stream_t stream) {
-  ABD_CHECK(a != nullptr && a->x, ABD_E_INVALID, "NULL x");
-  ABD_CHECK(train_mode || a->running, ABD_E_INVALID, "an eval forward needs the running statistics");
-  Ctx c;
-  if (int rc = make_rctx(net, a->batch, a->params, a->grads, a->running, train_mode ? a->num_batches_tracked : nullptr,
-                        workspace, workspace_bytes, stream, &c))
-    return rc;
-  if (int rc = run_forward(c, a->x, train_mode ? 1 : 0)) return rc;
-  return run_ce(c, nullptr, nullptr, false, 1.0f, a->logits_out, nullptr);
+  return stat_net_forward<Ctx>(net, a, train_mode, workspace, workspace_bytes, stream);
 }
 
 int abd_resnet_backward(abd_resnet* net, const abd_resnet_args* a, const float* dlogits, void* workspace,
                         size_t workspace_bytes, abd_stream_t stream) {
-  ABD_CHECK(a != nullptr && a->x && a->grads && dlogits, ABD_E_INVALID, "NULL x / grads / dlogits");
-  Ctx c;
-  if (int rc = make_rctx(net, a->batch, a->params, a->grads, nullptr, nullptr, workspace, workspace_bytes, stream, &c))
-    return rc;
-  return run_backward(c, a->x, dlogits);
+  return stat_net_backward<Ctx>(net, a, dlogits, workspace, workspace_bytes, stream);
 }
 
 int abd_resnet_train_step(abd_resnet* net, const abd_resnet_args* a, void* workspace, size_t workspace_bytes,
                           abd_stream_t stream) {
-  if (int rc = check_train_args(a)) return rc;
-  Ctx c;
-  if (int rc = make_rctx(net, a->batch, a->params, a->grads, a->running, a->num_batches_tracked, workspace,
-                        workspace_bytes, stream, &c))
-    return rc;
-  if (int rc = run_forward(c, a->x, 1)) return rc;
-  if (int rc = run_ce(c, a->labels, a->indicators, true, a->grad_scale, a->logits_out, a->metrics)) return rc;
-  if (int rc = run_backward(c, a->x, c.at<float>(c.L.dlogits))) return rc;
-  return adam_tail(a, net->off[P_COUNT], stream);
+  return stat_net_train_step<Ctx>(net, a, workspace, workspace_bytes, stream);
 }
 
 int abd_resnet_eval(abd_resnet* net, const float* x, int64_t batch, const float* params, const float* running,
                     const int64_t* labels, const int64_t* indicators, float* logits, int64_t* metrics, void* workspace,
                     size_t workspace_bytes, abd_stream_t stream) {
-  ABD_CHECK(x && logits && running, ABD_E_INVALID, "NULL x / logits / running");
-  Ctx c;
-  if (int rc = make_rctx(net, batch, params, nullptr, const_cast<float*>(running), nullptr, workspace, workspace_bytes,
-                        stream, &c))
-    return rc;
-  if (int rc = run_forward(c, x, 0)) return rc;
-  return run_ce(c, labels, indicators, false, 1.0f, logits, metrics);
+  return stat_net_eval<Ctx>(net, x, batch, params, running, labels, indicators, logits, metrics, workspace,
+                            workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -52,7 +52,6 @@ constexpr int kMaxSlices = 128;    // most slices of a conv weight gradient
 constexpr int kGemmSlices = 8;     // most slices of an LSTM weight gradient
 constexpr int kStatRows = 512;     // least pixels of one BatchNorm partial block
 constexpr int kStatBlocks = 256;   // most partial blocks of one BatchNorm reduction
-constexpr int kColsumRows = 512;   // above this many rows the column sums run in two stages
 constexpr int kLargeMinBlocks = 96;  // below this many 128 x 128 blocks the 64 x 64 GEMM tile fills more CUs
 constexpr int kW1Blocks = 512;     // most partial blocks of conv1's weight gradient
 constexpr int kC1 = 64, kC2 = 64, kC3 = 32;
@@ -71,121 +70,13 @@ constexpr float kDropP = 0.4f;
 enum { P_C1W, P_C1B, P_BN1W, P_BN1B, P_C2W, P_C2B, P_BN2W, P_BN2B, P_C3W, P_C3B, P_BN3W, P_BN3B,
        P_WIH0, P_WHH0, P_BIH0, P_BHH0, P_WIH1, P_WHH1, P_BIH1, P_BHH1, P_F1W, P_F1B, P_F2W, P_F2B, P_COUNT };
 
-// backward cell, sigmoid_acc, GemmArgs and its three forms, the host helpers; colsum_kernel, ce_kernel, metrics_kernel
+// backward cell, sigmoid_acc, colsum, weight_grad; GemmArgs and its three forms, keep_hash, the host helpers;
+// colsum_kernel, ce_kernel, metrics_kernel
 #include "lstm_common.inc"
-#include "gemm_tiled.inc"   // kBK, the tile sizes, f16v and launch_tiled
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-// the dropout hash of the other models: keep with probability 1 - p
-__device__ __forceinline__ bool keep_hash(uint64_t seed, uint64_t stream, uint64_t idx, float p) {
-  uint64_t z = seed ^ (stream * 0x9E3779B97F4A7C15ull) ^ (idx * 0xD1B54A32D192ED03ull);
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-  return u >= p;
-}
-
-// ------------------------------------------------------------------ LDS-tiled fp32 MFMA GEMM (GemmArgs)
-// An operand tile in LDS: [row][kBK + 1] when k is the contiguous index in memory, [k][rows + 32] when the row is.
-template <int TM, int TN>
-__global__ void __launch_bounds__(kT) gemm_tiled_kernel(GemmArgs a) {
-  constexpr int BM = 64 * TM, BN = 64 * TN;
-  constexpr int NA = BM * kBK / kT, NB = BN * kBK / kT;
-  __shared__ float As[kBK * (BM + 32)];
-  __shared__ float Bs[kBK * (BN + 32)];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wm = (w >> 1) * TM * 32, wn = (w & 1) * TN * 32;
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const int k0 = blockIdx.z * a.kchunk;
-  const int k1 = min(a.K, k0 + a.kchunk);
-  const bool a_kc = a.sak == 1, b_kc = a.sbk == 1;
-  const int a_sm = a_kc ? kBK + 1 : 1, a_sk = a_kc ? 1 : BM + 32;
-  const int b_sn = b_kc ? kBK + 1 : 1, b_sk = b_kc ? 1 : BN + 32;
-  f16v acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-  for (int kb = k0; kb < k1; kb += kBK) {
-    float ar[NA], br[NB];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int e = tid + i * kT;
-      const int m = a_kc ? e >> 5 : e % BM, k = a_kc ? e & 31 : e / BM;
-      const int gm = m0 + m, gk = kb + k;
-      ar[i] = (gm < a.M && gk < k1) ? a.A[(int64_t)gm * a.sam + (int64_t)gk * a.sak] : 0.0f;
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const int e = tid + i * kT;
-      const int n = b_kc ? e >> 5 : e % BN, k = b_kc ? e & 31 : e / BN;
-      const int gn = n0 + n, gk = kb + k;
-      float v = 0.0f;
-      if (gn < a.N && gk < k1) {
-        if (a.shift == 0) {
-          v = a.B[(int64_t)gk * a.sbk + (int64_t)gn * a.sbn];
-        } else {
-          const int ts = gk % a.T + a.shift;
-          if (ts >= 0 && ts < a.T) v = a.B[(int64_t)(gk + a.shift) * a.sbk + (int64_t)gn * a.sbn];
-        }
-      }
-      br[i] = v;
-    }
-    __syncthreads();   // the previous tile's operand reads are done
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const int e = tid + i * kT;
-      const int m = a_kc ? e >> 5 : e % BM, k = a_kc ? e & 31 : e / BM;
-      As[m * a_sm + k * a_sk] = ar[i];
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const int e = tid + i * kT;
-      const int n = b_kc ? e >> 5 : e % BN, k = b_kc ? e & 31 : e / BN;
-      Bs[n * b_sn + k * b_sk] = br[i];
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int kk = 0; kk < kBK / 2; ++kk) {
-      const int k = 2 * kk + (lane >> 5);
-      float av[TM], bv[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) av[i] = As[(wm + i * 32 + (lane & 31)) * a_sm + k * a_sk];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) bv[j] = Bs[(wn + j * 32 + (lane & 31)) * b_sn + k * b_sk];
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-    }
-  }
-  float* C = a.C + (int64_t)blockIdx.z * a.cz;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn + j * 32 + (lane & 31);
-    if (n >= a.N) continue;
-    float bias = 0.0f;
-    if (a.bias1) bias += a.bias1[n];
-    if (a.bias2) bias += a.bias2[n];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (m < a.M) {
-          float* c = C + (int64_t)m * a.ldc + n;
-          const float v = acc[i][j][r] + bias;
-          *c = a.accumulate ? *c + v : v;
-        }
-      }
-  }
-}
+#include "gemm_tiled_kernel.inc"   // kBK, the tile sizes, f16v, gemm_tiled_kernel and launch_gemm
+// f4v, tile_mfma, wgrad_reduce_kernel, blocks, stat_plan, the ABI entries of a net with running statistics
+#include "conv16_common.inc"
+#include "log_softmax.inc"   // lsm_fwd_kernel, lsm_bwd_kernel
 
 // ------------------------------------------------------------------ 2x2 conv as an implicit GEMM
 // The gather: pixel (b, h, w) of the Hr x Wr index map and tap (dy, dx) = (tap / 2, tap % 2) read pixel
@@ -206,20 +97,6 @@ __device__ __forceinline__ int64_t src_pixel(const ConvArgs& a, int b, int h, in
   const int nh = h + a.sign * (tap >> 1), nw = w + a.sign * (tap & 1);
   if ((unsigned)nh >= (unsigned)a.Hs || (unsigned)nw >= (unsigned)a.Ws) return -1;
   return ((int64_t)b * a.Hs + nh) * a.Ws + nw;
-}
-
-// As: (kBM rows) x kCK, pitch kLd; Bs: kCK x (16 TN), pitch ldb.  Operand lanes of the 16x16x4 product:
-// A[row lane & 15][k lane >> 4], B[k lane >> 4][col lane & 15]; acc[r] is row 4 (lane >> 4) + r, col lane & 15.
-template <int TN>
-__device__ __forceinline__ void tile_mfma(const float* As, const float* Bs, int ldb, int wm, int lane, f4v (&acc)[TN]) {
-#pragma unroll
-  for (int kk = 0; kk < kCK / 4; ++kk) {
-    const int k = kk * 4 + (lane >> 4);
-    const float av = As[(wm + (lane & 15)) * kLd + k];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-      acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, Bs[k * ldb + j * 16 + (lane & 15)], acc[j], 0, 0, 0);
-  }
 }
 
 template <int TN, int MODE>
@@ -318,7 +195,7 @@ __global__ void __launch_bounds__(kT) conv_kernel(ConvArgs a) {
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) part[j][r] = 0.0f;
-    tile_mfma<TN>(As, Bs, LDB, wm, lane, part);
+    tile_mfma<TN, kCK>(As, Bs, LDB, wm, lane, part);
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -360,17 +237,6 @@ __global__ void __launch_bounds__(kT) repack_kernel(RepackArgs a) {
   const float v = a.w[u][e];
   a.wf[u][((int64_t)tap * Cin + ci) * Cout + co] = v;
   if (a.need_wd) a.wd[u][((int64_t)tap * Cout + co) * Cin + ci] = v;
-}
-
-// dw (Cout, Cin, 2, 2) = the sum over slices, in slice order, of slab (slice, tap, Cin, Cout)
-__global__ void __launch_bounds__(kT) wgrad_reduce_kernel(const float* slab, int slices, int Cout, int Cin, float* dw) {
-  const int e = blockIdx.x * kT + threadIdx.x;
-  const int per = 4 * Cout * Cin;
-  if (e >= per) return;
-  double s = 0.0;
-  for (int z = 0; z < slices; ++z) s += (double)slab[(int64_t)z * per + e];
-  const int co = e % Cout, ci = (e / Cout) % Cin, tap = e / (Cout * Cin);
-  dw[((int64_t)co * Cin + ci) * 4 + tap] = (float)s;
 }
 
 // conv1: z (B, H1, W1, 64) = relu(bias + the four taps of x (B, H, W)); one thread per output value
@@ -626,29 +492,6 @@ __global__ void __launch_bounds__(kT) dropout_bwd_kernel(float* dseq, const uint
   dseq[e] = keep[b * per + ((int64_t)c * TS + t) * Wf + w] ? dseq[e] * (1.0f / (1.0f - kDropP)) : 0.0f;
 }
 
-__global__ void __launch_bounds__(64) lsm_fwd_kernel(const float* z, float* lp, int K) {
-  const int row = blockIdx.x, lane = threadIdx.x;
-  const float* zr = z + (int64_t)row * K;
-  float mx = -INFINITY;
-  for (int j = lane; j < K; j += 64) mx = fmaxf(mx, zr[j]);
-  mx = abd::wave_max(mx);
-  float se = 0.0f;
-  for (int j = lane; j < K; j += 64) se += expf(zr[j] - mx);
-  se = abd::wave_sum(se);
-  const float lse = __ocml_log_f32(se);
-  for (int j = lane; j < K; j += 64) lp[(int64_t)row * K + j] = (zr[j] - mx) - lse;
-}
-
-// dz = dlp - exp(lp) * sum(dlp)
-__global__ void __launch_bounds__(64) lsm_bwd_kernel(const float* lp, const float* dlp, float* dz, int K) {
-  const int row = blockIdx.x, lane = threadIdx.x;
-  const int64_t o = (int64_t)row * K;
-  float s = 0.0f;
-  for (int j = lane; j < K; j += 64) s += dlp[o + j];
-  s = abd::wave_sum(s);
-  for (int j = lane; j < K; j += 64) dz[o + j] = dlp[o + j] - expf(lp[o + j]) * s;
-}
-
 // ------------------------------------------------------------------ recurrence
 struct RecArgs {
   float* gates;        // [B*T][512]: x_t W_ih^T + b_ih + b_hh on entry; activated i f g o after the forward
@@ -852,13 +695,6 @@ Layout make_layout(const abd_smalllstm* n, int64_t B) {
   return L;
 }
 
-struct Drop {
-  const uint8_t* mask_in;
-  uint8_t* mask_out;
-  uint64_t seed, counter;
-  int64_t row_offset;
-};
-
 struct Ctx : CtxBase {
   const abd_smalllstm* n;
   Layout L;
@@ -868,33 +704,6 @@ struct Ctx : CtxBase {
   float* g(int i) const { return grads + n->off[i]; }
   float* gb(int i) const { return at<float>(L.g[i]); }
 };
-
-inline unsigned blocks(int64_t n) { return (unsigned)((n + kT - 1) / kT); }
-
-int launch_gemm(hipStream_t s, GemmArgs g, int ksplit = 1) {
-  if (g.M <= 0 || g.N <= 0) return ABD_OK;
-  ksplit = std::max(1, ksplit);
-  if (ksplit == 1) g.kchunk = std::max(g.K, 1);
-  return launch_tiled(s, g.M, g.N, ksplit, kLargeMinBlocks, gemm_tiled_kernel<1, 1>, gemm_tiled_kernel<2, 2>, g);
-}
-
-int colsum(const Ctx& c, const float* A, int64_t rows, int64_t cols, int64_t ld, float* out) {
-  return launch_colsum(c, A, rows, cols, ld, out, 0, kGates, kColsumRows);
-}
-
-// dW[j][i] = sum_rows dg[row][j] act[row][i] over all B*T rows, sliced (shift -1: act one step back)
-int weight_grad(const Ctx& c, const float* dg, const float* act, int in, int shift, float* out) {
-  const int64_t BT = c.B * c.n->TS;
-  GemmArgs g = gemm_tn(dg, act, in, out, kGates, in, BT);
-  g.T = c.n->TS;
-  g.shift = shift;
-  if (c.L.ksplit <= 1) return launch_gemm(c.s, g);
-  g.C = c.at<float>(c.L.slab);
-  g.cz = (int64_t)kGates * in;
-  g.kchunk = (int)c.L.kchunk;
-  if (int rc = launch_gemm(c.s, g, c.L.ksplit)) return rc;
-  return colsum(c, g.C, c.L.ksplit, g.cz, g.cz, out);
-}
 
 template <int MODE>
 int launch_conv(const Ctx& c, const ConvArgs& a, int N, int M, int nz) {
@@ -945,20 +754,9 @@ int conv_wgrad(const Ctx& c, int i, const float* dz) {
   a.Hr = q.Ho, a.Wr = q.Wo, a.Hs = q.Hi, a.Ws = q.Wi, a.C = q.Cin, a.sign = 1;
   a.pixels = (int)pixels, a.kchunk = (int)sl.kchunk;
   if (int rc = launch_conv<2>(c, a, q.Cout, 4 * q.Cin, sl.ksplit)) return rc;
-  wgrad_reduce_kernel<<<blocks(4 * q.Cin * q.Cout), kT, 0, c.s>>>(a.out, sl.ksplit, q.Cout, q.Cin, c.g(4 * i));
+  wgrad_reduce_kernel<4><<<blocks(4 * q.Cin * q.Cout), kT, 0, c.s>>>(a.out, sl.ksplit, q.Cout, q.Cin, c.g(4 * i));
   ABD_LAUNCH_CHECK();
   return ABD_OK;
-}
-
-struct StatPlan {
-  int nb;
-  int64_t chunk;
-};
-StatPlan stat_plan(int64_t pixels) {
-  StatPlan p;
-  p.nb = (int)std::max<int64_t>(1, std::min<int64_t>(kStatBlocks, (pixels + kStatRows - 1) / kStatRows));
-  p.chunk = (pixels + p.nb - 1) / p.nb;
-  return p;
 }
 
 PoolArgs pool_geo(const abd_smalllstm* n, int i) {
@@ -1031,7 +829,8 @@ RecArgs rec_args(const Ctx& c, int l) {
   return r;
 }
 
-int run_forward(const Ctx& c, const float* x, int train, const Drop& d) {
+// a: the call's args struct, whose dropout fields a train-mode forward reads; NULL for eval
+int run_forward(const Ctx& c, const float* x, int train, const abd_smalllstm_args* a) {
   const abd_smalllstm* n = c.n;
   const int64_t B = c.B;
   RepackArgs ra{};
@@ -1055,6 +854,8 @@ int run_forward(const Ctx& c, const float* x, int train, const Drop& d) {
   const int64_t BT = B * TS;
   float* seq = c.at<float>(c.L.seq);
   e = BT * n->F;
+  const abd_smalllstm_args none{};
+  const abd_smalllstm_args& d = a ? *a : none;
   dropout_fwd_kernel<<<blocks(e), kT, 0, c.s>>>(c.at<float>(c.L.p[2]), seq, e, TS, n->Wf, train, d.mask_in,
                                                 c.at<uint8_t>(c.L.keep), d.mask_out, d.seed, d.counter, d.row_offset);
   ABD_LAUNCH_CHECK();
@@ -1109,9 +910,9 @@ int run_backward(const Ctx& c, const float* x, const float* dlogp) {
     const float* in = l ? c.at<float>(c.L.h[l - 1]) : c.at<float>(c.L.seq);
     const int width = l ? kHid : n->F;
     const int base = P_WIH0 + 4 * l;
-    if (int rc = weight_grad(c, r.gates, in, width, 0, c.g(base))) return rc;
+    if (int rc = weight_grad(c, TS, r.gates, in, width, 0, c.g(base))) return rc;
     if (TS > 1) {
-      if (int rc = weight_grad(c, r.gates, r.h, kHid, -1, c.g(base + 1))) return rc;
+      if (int rc = weight_grad(c, TS, r.gates, r.h, kHid, -1, c.g(base + 1))) return rc;
     } else {
       ABD_HIP(hipMemsetAsync(c.g(base + 1), 0, sizeof(float) * kGates * kHid, c.s));
     }
@@ -1144,15 +945,10 @@ int run_backward(const Ctx& c, const float* x, const float* dlogp) {
   return ABD_OK;
 }
 
-int make_sctx(const abd_smalllstm* net, int64_t B, const float* params, float* grads, float* running, int64_t* nbt,
-              void* ws, size_t bytes, abd_stream_t stream, Ctx* c) {
-  if (int rc = make_ctx(net, B, params, grads, ws, bytes, stream, kC1, make_layout, c)) return rc;
-  c->running = running;
-  c->nbt = nbt;
-  return ABD_OK;
+int make_ctx(const abd_smalllstm* net, int64_t B, const float* params, float* grads, void* ws, size_t bytes,
+             abd_stream_t stream, Ctx* c) {
+  return make_ctx(net, B, params, grads, ws, bytes, stream, kC1, make_layout, c);
 }
-
-Drop drop_of(const abd_smalllstm_args* a) { return Drop{a->mask_in, a->mask_out, a->seed, a->counter, a->row_offset}; }
 
 }  // namespace
 
@@ -1248,48 +1044,24 @@ int64_t abd_smalllstm_workspace_offset(const abd_smalllstm* net, int64_t batch, 
 
 int abd_smalllstm_forward(abd_smalllstm* net, const abd_smalllstm_args* a, int train_mode, void* workspace,
                           size_t workspace_bytes, abd_stream_t stream) {
-  ABD_CHECK(a != nullptr && a->x, ABD_E_INVALID, "NULL x");
-  ABD_CHECK(train_mode || a->running, ABD_E_INVALID, "an eval forward needs the running statistics");
-  Ctx c;
-  if (int rc = make_sctx(net, a->batch, a->params, a->grads, a->running, train_mode ? a->num_batches_tracked : nullptr,
-                        workspace, workspace_bytes, stream, &c))
-    return rc;
-  if (int rc = run_forward(c, a->x, train_mode ? 1 : 0, drop_of(a))) return rc;
-  return run_ce(c, nullptr, nullptr, false, 1.0f, a->logits_out, nullptr);
+  return stat_net_forward<Ctx>(net, a, train_mode, workspace, workspace_bytes, stream);
 }
 
 int abd_smalllstm_backward(abd_smalllstm* net, const abd_smalllstm_args* a, const float* dlogits, void* workspace,
                            size_t workspace_bytes, abd_stream_t stream) {
-  ABD_CHECK(a != nullptr && a->x && a->grads && dlogits, ABD_E_INVALID, "NULL x / grads / dlogits");
-  Ctx c;
-  if (int rc = make_sctx(net, a->batch, a->params, a->grads, nullptr, nullptr, workspace, workspace_bytes, stream, &c))
-    return rc;
-  return run_backward(c, a->x, dlogits);
+  return stat_net_backward<Ctx>(net, a, dlogits, workspace, workspace_bytes, stream);
 }
 
 int abd_smalllstm_train_step(abd_smalllstm* net, const abd_smalllstm_args* a, void* workspace, size_t workspace_bytes,
                              abd_stream_t stream) {
-  if (int rc = check_train_args(a)) return rc;
-  Ctx c;
-  if (int rc = make_sctx(net, a->batch, a->params, a->grads, a->running, a->num_batches_tracked, workspace,
-                        workspace_bytes, stream, &c))
-    return rc;
-  if (int rc = run_forward(c, a->x, 1, drop_of(a))) return rc;
-  if (int rc = run_ce(c, a->labels, a->indicators, true, a->grad_scale, a->logits_out, a->metrics)) return rc;
-  if (int rc = run_backward(c, a->x, c.at<float>(c.L.dlogits))) return rc;
-  return adam_tail(a, net->off[P_COUNT], stream);
+  return stat_net_train_step<Ctx>(net, a, workspace, workspace_bytes, stream);
 }
 
 int abd_smalllstm_eval(abd_smalllstm* net, const float* x, int64_t batch, const float* params, const float* running,
                        const int64_t* labels, const int64_t* indicators, float* logits, int64_t* metrics,
                        void* workspace, size_t workspace_bytes, abd_stream_t stream) {
-  ABD_CHECK(x && logits && running, ABD_E_INVALID, "NULL x / logits / running");
-  Ctx c;
-  if (int rc = make_sctx(net, batch, params, nullptr, const_cast<float*>(running), nullptr, workspace, workspace_bytes,
-                        stream, &c))
-    return rc;
-  if (int rc = run_forward(c, x, 0, Drop{})) return rc;
-  return run_ce(c, labels, indicators, false, 1.0f, logits, metrics);
+  return stat_net_eval<Ctx>(net, x, batch, params, running, labels, indicators, logits, metrics, workspace,
+                            workspace_bytes, stream);
 }
 
 }  // extern "C"

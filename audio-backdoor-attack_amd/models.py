@@ -112,6 +112,19 @@ def dropout_seed(device, model=None) -> int:
     return (base + nonce * 0x9E3779B97F4A7C15) & ((1 << 63) - 1)
 
 
+def dropout_step(model, a, device, seed=None, mask=None, mask_out=None):
+    """The dropout fields of the args struct `a` for model's next train-mode launch: the hash seed (dropout_seed
+    unless given) and the step counter, which advances; for a model with one mask, the given keep mask in place of
+    the hash and the buffer that receives the mask used."""
+    a.seed = dropout_seed(device, model) if seed is None else seed
+    a.counter = model._step
+    model._step += 1
+    if mask is not None:
+        a.mask_in = mask.data_ptr()
+    if mask_out is not None:
+        a.mask_out = mask_out.data_ptr()
+
+
 DROPOUT_SOURCES = ("device", "torch_cpu")
 
 
@@ -276,9 +289,7 @@ class smallcnn(nn.Module):
         ws = eng.workspace(B)
         a = self._args(eng, x, B)
         a.logprobs_out = out.data_ptr()
-        a.seed = dropout_seed(x.device, self) if seed is None else seed
-        a.counter = self._step
-        self._step += 1
+        dropout_step(self, a, x.device, seed)
         if mask1 is None:
             hm = self.step_masks(B, x.device)
             if hm is not None:

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _flat, _lib as L
-from .models import DROPOUT_SOURCES, draw_dropout_nonce, dropout_seed
+from .models import DROPOUT_SOURCES, dropout_step
 
 CONVS = (("conv1", 1, 96), ("conv2", 96, 256), ("conv3", 256, 384), ("conv4", 384, 384), ("conv5", 384, 256))
 FC1, FC2 = 256, 128
@@ -64,6 +64,7 @@ class largecnn(_flat.FlatModule, nn.Module):
     PARAM_ORDER, ARGS, ENGINE = PARAM_ORDER, L.LargeCnnArgs, _Engine
     BACKWARD_ORDER = ("largecnn backward must directly follow its train-mode forward (activations live in the shared "
                       "workspace)")
+    STATE = _flat.DROPOUT_STATE + (("dropout_source", "device"),)
 
     def __init__(self, num_classes, linear_features):
         super().__init__()
@@ -83,13 +84,6 @@ class largecnn(_flat.FlatModule, nn.Module):
         self.fc3 = nn.Linear(in_features=FC2, out_features=num_classes)
         self._init_abd()
 
-    def _init_abd(self):
-        self._engine = None
-        self._step = 0
-        self._dropout_nonce = None
-        self.gemm_precision = "f32"
-        self.dropout_source = "device"
-
     # ------------------------------------------------------------------ settings
     def set_dropout_source(self, source: str):
         """'device' (default): the keep-masks come from the counter-based hash on the GPU.  'torch_cpu':
@@ -108,14 +102,6 @@ class largecnn(_flat.FlatModule, nn.Module):
         m2 = torch.empty((batch, FC2)).bernoulli_(0.5).to(torch.uint8)
         return m1.to(device, non_blocking=True), m2.to(device, non_blocking=True)
 
-    def __setstate__(self, state):
-        # also the target of reference-format checkpoints (training.reference_pickle_object)
-        super().__setstate__(state)
-        for k, v in (("_engine", None), ("_step", 0), ("gemm_precision", "f32"), ("dropout_source", "device"),
-                     ("_dropout_nonce", None)):
-            if k not in self.__dict__:
-                self.__dict__[k] = v
-
     # ------------------------------------------------------------------ binding
     def engine(self, x: torch.Tensor) -> _Engine:
         """Bind (or re-bind) the parameters to the flat device buffer for x's geometry."""
@@ -124,11 +110,7 @@ class largecnn(_flat.FlatModule, nn.Module):
         if want != self.fc1.in_features:
             raise ValueError(f"input ({H}, {W}) gives fc1 {want} features but the model was built for "
                              f"linear_features {self.fc1.in_features}")
-        bound = self._engine
-        eng = self._bind(H, W, x.device)
-        if eng is not bound and getattr(self, "_dropout_nonce", None) is None:
-            self._dropout_nonce = draw_dropout_nonce(x.device)
-        return eng
+        return self._bind_dropout(H, W, x.device)
 
     # ------------------------------------------------------------------ launches
     def hip_forward(self, x, train: bool, seed: int | None = None, masks=None, masks_out=None):
@@ -143,9 +125,7 @@ class largecnn(_flat.FlatModule, nn.Module):
         ws = eng.workspace(B)
         a = self._args(eng, x, B)
         a.logits_out = out.data_ptr()
-        a.seed = dropout_seed(x.device, self) if seed is None else seed
-        a.counter = self._step
-        self._step += 1
+        dropout_step(self, a, x.device, seed)
         if masks is None:
             masks = self.step_masks(B, x.device)
             self._host_masks = masks  # keep alive until the launch has consumed them

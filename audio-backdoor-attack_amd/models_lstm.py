@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _flat, _lib as L
-from .models import DROPOUT_SOURCES, draw_dropout_nonce, dropout_seed
+from .models import DROPOUT_SOURCES, dropout_step
 
 _RNN = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
         "weight_ih_l0_reverse", "weight_hh_l0_reverse", "bias_ih_l0_reverse", "bias_hh_l0_reverse")
@@ -56,6 +56,7 @@ class lstmwithattention(_flat.FlatModule, nn.Module):
     PARAM_ORDER, RUNNING_ORDER, ARGS, ENGINE = PARAM_ORDER, RUNNING_ORDER, L.LstmAttnArgs, _Engine
     BACKWARD_ORDER = ("lstmwithattention backward must directly follow its train-mode forward (activations live in "
                       "the shared workspace)")
+    STATE = _flat.DROPOUT_STATE + (("dropout_source", "device"),)
 
     def __init__(self, classes, time_len, seq_len):
         super().__init__()
@@ -71,11 +72,7 @@ class lstmwithattention(_flat.FlatModule, nn.Module):
         self.dropout = nn.Dropout(0.5)
         self.dense3 = nn.Linear(64, 32)
         self.output = nn.Linear(32, classes)
-        self._engine = None
-        self._step = 0
-        self._dropout_nonce = None
-        self.gemm_precision = "f32"
-        self.dropout_source = "device"
+        self._init_abd()
 
     # ------------------------------------------------------------------ settings
     def set_gemm_precision(self, precision: str):
@@ -102,14 +99,6 @@ class lstmwithattention(_flat.FlatModule, nn.Module):
             return None
         return torch.empty((batch, 64)).bernoulli_(0.5).to(torch.uint8).to(device, non_blocking=True)
 
-    def __setstate__(self, state):
-        # also the target of reference-format checkpoints (training.reference_pickle_object)
-        super().__setstate__(state)
-        for k, v in (("_engine", None), ("_step", 0), ("gemm_precision", "f32"), ("dropout_source", "device"),
-                     ("_dropout_nonce", None)):
-            if k not in self.__dict__:
-                self.__dict__[k] = v
-
     # ------------------------------------------------------------------ binding
     def engine(self, x: torch.Tensor) -> _Engine:
         """Bind (or re-bind) the parameters to flat device buffers for x's geometry."""
@@ -117,11 +106,7 @@ class lstmwithattention(_flat.FlatModule, nn.Module):
         if T != self.dense2.in_features or F != self.rnn1.input_size:
             raise ValueError(f"input (T, F) = ({T}, {F}) but the model was built for seq_len "
                              f"{self.dense2.in_features}, time_len {self.rnn1.input_size}")
-        bound = self._engine
-        eng = self._bind(T, F, x.device)
-        if eng is not bound and getattr(self, "_dropout_nonce", None) is None:
-            self._dropout_nonce = draw_dropout_nonce(x.device)
-        return eng
+        return self._bind_dropout(T, F, x.device)
 
     # ------------------------------------------------------------------ launches
     def _check_input(self, x):
@@ -139,16 +124,11 @@ class lstmwithattention(_flat.FlatModule, nn.Module):
         ws = eng.workspace(B)
         a = self._args(eng, x, B)
         a.logits_out = out.data_ptr()
-        a.seed = dropout_seed(x.device, self) if seed is None else seed
-        a.counter = self._step
-        self._step += 1
+        dropout_step(self, a, x.device, seed, mask, mask_out)
         if mask is None:
-            mask = self.step_mask(B, x.device)
-            self._host_mask = mask  # keep alive until the launch has consumed it
-        if mask is not None:
-            a.mask_in = mask.data_ptr()
-        if mask_out is not None:
-            a.mask_out = mask_out.data_ptr()
+            self._host_mask = self.step_mask(B, x.device)  # kept alive until the launch has consumed it
+            if self._host_mask is not None:
+                a.mask_in = self._host_mask.data_ptr()
         eng.call("forward", C.byref(a), 1, ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
         eng.token += 1
         eng.last_train_token = eng.token

@@ -139,18 +139,6 @@ class ResNet(_flat.FlatModule, nn.Module):
             layers.append(block(out_channels, out_channels))
         return nn.Sequential(*layers)
 
-    def _init_abd(self):
-        self._engine = None
-        self.gemm_precision = "f32"
-
-    # ------------------------------------------------------------------ settings
-    def __setstate__(self, state):
-        # also the target of reference-format checkpoints (training.reference_pickle_object)
-        super().__setstate__(state)
-        for k, v in (("_engine", None), ("gemm_precision", "f32")):
-            if k not in self.__dict__:
-                self.__dict__[k] = v
-
     # ------------------------------------------------------------------ binding
     def engine(self, x: torch.Tensor) -> _Engine:
         """Bind (or re-bind) the parameters and running statistics to flat device buffers for x's geometry."""

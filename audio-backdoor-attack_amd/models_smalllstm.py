@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _flat, _lib as L
-from .models import draw_dropout_nonce, dropout_seed
+from .models import dropout_step
 
 HIDDEN, LAYERS, FC1_IN, DROP_P = 128, 2, 224, 0.4
 # (conv, bn, Cin, Cout)
@@ -83,6 +83,7 @@ class smalllstm(_flat.FlatModule, nn.Module):
     BACKWARD_ORDER = ("smalllstm backward must directly follow its train-mode forward (activations live in the "
                       "shared workspace, and backward consumes them)")
     BACKWARD_CONSUMES = True   # the saved gates hold the gate gradients afterwards
+    STATE = _flat.DROPOUT_STATE
 
     def __init__(self, num_classes, rnn_features):
         super().__init__()
@@ -104,19 +105,6 @@ class smalllstm(_flat.FlatModule, nn.Module):
         self.softmax = nn.Softmax()
         self._init_abd()
 
-    def _init_abd(self):
-        self._engine = None
-        self._step = 0
-        self._dropout_nonce = None
-        self.gemm_precision = "f32"
-
-    def __setstate__(self, state):
-        # also the target of reference-format checkpoints (training.reference_pickle_object)
-        super().__setstate__(state)
-        for k, v in (("_engine", None), ("_step", 0), ("gemm_precision", "f32"), ("_dropout_nonce", None)):
-            if k not in self.__dict__:
-                self.__dict__[k] = v
-
     # ------------------------------------------------------------------ binding
     def engine(self, x: torch.Tensor) -> _Engine:
         """Bind (or re-bind) the parameters and running statistics to flat device buffers for x's geometry."""
@@ -125,11 +113,7 @@ class smalllstm(_flat.FlatModule, nn.Module):
         if want != self.rnn.input_size:
             raise ValueError(f"input ({H}, {W}) gives the LSTM {want} features but the model was built for "
                              f"rnn_features {self.rnn.input_size}")
-        bound = self._engine
-        eng = self._bind(H, W, x.device)
-        if eng is not bound and getattr(self, "_dropout_nonce", None) is None:
-            self._dropout_nonce = draw_dropout_nonce(x.device)
-        return eng
+        return self._bind_dropout(H, W, x.device)
 
     def mask_shape(self, x):
         """(B, 32, T, Wf): drop1's input in the reference, the shape of a keep mask."""
@@ -152,13 +136,7 @@ class smalllstm(_flat.FlatModule, nn.Module):
         ws = eng.workspace(B)
         a = self._args(eng, x, B)
         a.logits_out = out.data_ptr()
-        a.seed = dropout_seed(x.device, self) if seed is None else seed
-        a.counter = self._step
-        self._step += 1
-        if mask is not None:
-            a.mask_in = mask.data_ptr()
-        if mask_out is not None:
-            a.mask_out = mask_out.data_ptr()
+        dropout_step(self, a, x.device, seed, mask, mask_out)
         eng.call("forward", C.byref(a), 1, ws.data_ptr(), ws.numel(), L.stream_ptr(x.device))
         eng.token += 1
         eng.last_train_token = eng.token

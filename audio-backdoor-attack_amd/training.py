@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .models import smallcnn, dropout_seed
+from .models import smallcnn, dropout_seed, dropout_step
 from .models_lstm import lstmwithattention
 from .models_rnn import RNN
 from .models_largecnn import largecnn, adopt, adoptable
@@ -205,9 +205,7 @@ def train_step(model: smallcnn, x, labels, indicators, adam: AdamBinding | None,
             adam.step += 1
             a.adam_step = adam.step
             a.do_update = 1
-    a.seed = dropout_seed(x.device, model) if seed is None else seed
-    a.counter = model._step
-    model._step += 1
+    dropout_step(model, a, x.device, seed)
     a.row_offset = int(row_offset)
     if bn_sync is not None:
         bn_sync.bind(a)
@@ -263,15 +261,11 @@ def lstm_train_step(model: lstmwithattention, x, labels, indicators, adam: AdamB
                     logits_out=None):
     """One fused device step of lstmwithattention (forward + CE + backward [+ Adam]) through the C ABI."""
     eng, a = _flat_step_args(model, x, labels, indicators, adam, metrics, do_update, grad_scale, logits_out)
-    a.seed = dropout_seed(x.device, model) if seed is None else seed
-    a.counter = model._step
-    model._step += 1
+    dropout_step(model, a, x.device, seed, mask, mask_out)
     if mask is None:
         mask = model.step_mask(x.shape[0], x.device)
-    if mask is not None:
-        a.mask_in = mask.data_ptr()
-    if mask_out is not None:
-        a.mask_out = mask_out.data_ptr()
+        if mask is not None:
+            a.mask_in = mask.data_ptr()
     return _flat_step(eng, a, x)
 
 
@@ -292,9 +286,7 @@ def largecnn_train_step(model: largecnn, x, labels, indicators, adam: AdamBindin
     model._check_input(x)
     eng, a = _flat_step_args(model, x, labels, indicators, adam, metrics, do_update, grad_scale, logits_out)
     eng.last_train_token = -1   # the step overwrites the workspace a pending autograd backward would read
-    a.seed = dropout_seed(x.device, model) if seed is None else seed
-    a.counter = model._step
-    model._step += 1
+    dropout_step(model, a, x.device, seed)
     if masks is None:
         masks = model.step_masks(x.shape[0], x.device)
     if masks is not None:
@@ -325,13 +317,7 @@ def smalllstm_train_step(model: smalllstm, x, labels, indicators, adam: AdamBind
     x = x.contiguous()
     eng, a = _flat_step_args(model, x, labels, indicators, adam, metrics, do_update, grad_scale, logits_out)
     eng.last_train_token = -1   # the step overwrites the workspace a pending autograd backward would read
-    a.seed = dropout_seed(x.device, model) if seed is None else seed
-    a.counter = model._step
-    model._step += 1
-    if mask is not None:
-        a.mask_in = mask.data_ptr()
-    if mask_out is not None:
-        a.mask_out = mask_out.data_ptr()
+    dropout_step(model, a, x.device, seed, mask, mask_out)
     return _flat_step(eng, a, x)
 
 

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Byte equality of two libabd builds on the four flat-buffer backbones (RNN, largecnn, ResNet, lstmwithattention).
+"""Byte equality of two libabd builds on the five flat-buffer backbones (RNN, largecnn, ResNet, lstmwithattention,
+smalllstm).
 
     ABD_LIB=/path/libabd_parent.so timeout -k 10 120 python scripts/backbone_equal.py dump out/parent.npz
     ABD_LIB=/path/libabd.so        timeout -k 10 120 python scripts/backbone_equal.py dump out/new.npz
@@ -18,6 +19,9 @@ differences; it exits 1 on any difference.
                       whose generated masks are written out
     ResNet            every case of tests/resnet_cases.py: eval forward, two Adam train steps
     lstmwithattention `tiny` and `ragged_tiles` of tests/lstm_attention_cases.py: eval forward, two Adam train steps
+    smalllstm         every case of tests/smalllstm_cases.py: eval forward, an Adam step with the case's mask, a step
+                      whose generated mask is written out under a fixed seed, eval forward on the updated running
+                      statistics; the running statistics and num_batches_tracked after each step
 """
 from __future__ import annotations
 
@@ -40,10 +44,12 @@ def dump(path):
     from abd_amd.models_lstm import lstmwithattention
     from abd_amd.models_resnet import ResNet, ResidualBlock
     from abd_amd.models_rnn import RNN
+    from abd_amd.models_smalllstm import smalllstm
     import largecnn_cases as lc
     import lstm_attention_cases as ac
     import resnet_cases as rc
     import rnn_cases as nc
+    import smalllstm_cases as sc
 
     dev = torch.device("cuda")
     rec = {}
@@ -137,6 +143,22 @@ def dump(path):
         eval_forward(tag, m, x)
         steps(tag, m, x, y, ind, lambda adam, mt, lo: T.lstm_train_step(m, x, y, ind, adam, mt, mask=mask,
                                                                         logits_out=lo))
+        del m
+    # ---------------------------------------------------------------- smalllstm
+    for name, (B, H, W, K, _) in sc.CASES.items():
+        m = load(smalllstm(K, sc.rnn_features(H, W)), sc.make_state(name))
+        x, y, ind, mask = dev_t(*sc.make_inputs(name))
+        tag = f"smalllstm/{name}"
+        eval_forward(tag, m, x)
+        steps(tag, m, x, y, ind, lambda adam, mt, lo: T.smalllstm_train_step(m, x, y, ind, adam, mt, mask=mask,
+                                                                             logits_out=lo), n=1)
+        mo = torch.zeros_like(mask)
+        lo = torch.zeros((B, K), dtype=torch.float32, device=dev)
+        T.smalllstm_train_step(m, x, y, ind, None, None, mask_out=mo, do_update=False, seed=77, logits_out=lo)
+        put(f"{tag}/hash/logits", lo)
+        put(f"{tag}/hash/mask", mo)
+        engine_state(f"{tag}/hash", m, ("grads", "running", "nbt"))
+        eval_forward(f"{tag}/after", m, x)
         del m
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
